@@ -19,6 +19,14 @@ import pytest
 import torch
 
 
+@pytest.fixture(autouse=True)
+def _gloo_backend(monkeypatch):
+    """These tests are about the merge protocol over gloo. The spawned
+    workers inherit this; without it a machine with one visible GPU picks
+    RCCL and refuses two ranks on the same device."""
+    monkeypatch.setenv("ANOVOS_AMD_DIST_BACKEND", "gloo")
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

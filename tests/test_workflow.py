@@ -246,3 +246,46 @@ def test_bench_json_contract():
     # whole-job aggregate: rows_per_gpu * n_gpus / (ms_per_step/1000)
     expect = j["config"]["rows_per_gpu"] * j["n_gpus"] / (j["ms_per_step"] / 1000.0)
     assert j["value"] == pytest.approx(expect, rel=1e-6)
+
+
+def test_bench_full_and_dump_outputs(tmp_path):
+    """A plain run prints the result line only; --full adds the
+    per-section breakdown; --dump-outputs writes the last timed step's
+    results as float .npy files that repeat exactly from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(out_dir, *extra):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+                            "--steps", "1", "--warmup", "0", "--rows", "5000",
+                            "--dump-outputs", str(out_dir), *extra],
+                           capture_output=True, text=True, timeout=600, cwd=repo)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+
+    plain = run(tmp_path / "a")
+    full = run(tmp_path / "b", "--full")
+    assert len(plain) == 1 and plain[0]["steps"] == 1 and plain[0]["ms_per_step"] > 0
+    assert len(full) == 2 and "sections_ms_per_step" in full[0] and full[1]["metric"] == plain[0]["metric"]
+
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"correlation.npy", "iv.npy", "quantiles.npy", "binned.npy", "z_standardization.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, n
+        assert np.isfinite(a).all(), n
+        assert np.array_equal(a, b, equal_nan=True), n
+        total += a.nbytes
+    assert total <= 64 * 2**20
+    assert np.load(tmp_path / "a" / "correlation.npy").shape == (150, 150)
+    # nulls survive as marks next to the zeroed cells (1% of the data is null)
+    z, marks = np.load(tmp_path / "a" / "z_standardization.npy"), np.load(tmp_path / "a" / "z_standardization_nonfinite.npy")
+    assert marks.shape == z.shape and set(np.unique(marks)) == {0.0, 1.0} and (z[marks == 1] == 0).all()
