@@ -73,8 +73,11 @@ def _finish_output(idf: AnovosFrame, odf: AnovosFrame, list_of_cols, postfix: st
     out = {}
     for name in odf.columns:
         if name in replaced:
-            newc = odf.col(name + postfix).clone()
+            src = odf.col(name + postfix)
+            newc = src.clone()
             newc.name = name
+            if ("bincounts",) in src.cache:  # same tensor, so the counts still hold
+                newc.cache[("bincounts",)] = src.cache[("bincounts",)]
             out[name] = newc
         elif name.endswith(postfix) and name[: -len(postfix)] in replaced:
             continue  # consumed above
@@ -158,9 +161,14 @@ def attribute_binning(
     cuts = [torch.tensor(bc, dtype=torch.float64) for bc in bin_cutoffs]
     odf = idf
     if bin_dtype == "numerical":
-        vals_all = bucketize_ops.bucketize_columns_float(tensors, cuts)  # fused bin+1/NaN
-        for c, vals in zip(list_of_cols, vals_all):
-            odf = odf.with_column(c + "_binned", Column(c + "_binned", "int", vals))
+        # fused bin+1/NaN; the same pass counts every bin, and each binned
+        # column carries its (device, rank-local) count row so the drift
+        # frequency pass need not re-read the binned frame
+        vals_all, bin_counts = bucketize_ops.bucketize_columns_float_counts(tensors, cuts)
+        for i, (c, vals) in enumerate(zip(list_of_cols, vals_all)):
+            newc = Column(c + "_binned", "int", vals)
+            newc.cache[("bincounts",)] = bin_counts[i, : len(bin_cutoffs[i]) + 2]
+            odf = odf.with_column(c + "_binned", newc)
         bins = []
     else:
         bins = bucketize_ops.bucketize_columns(tensors, cuts)  # 0..len(cuts), -1 null

@@ -166,19 +166,63 @@ def _key_order(k):
         return (1, 0.0, str(k))
 
 
+def _cached_bin_counts(binned_idf, num_cols):
+    """Global per-slot counts (python int lists: slot 0 nulls, slot b =
+    bin label b) for binned numeric columns, from the count rows
+    attribute_binning's kernel left in each Column.cache: one stack, one
+    all-reduce, one device->host copy. None when any column lacks its row
+    (frame read back from disk, cleared cache, column binned elsewhere) —
+    the caller then histograms all of them."""
+    if not num_cols:
+        return None
+    rows = [binned_idf.col(c).cache.get(("bincounts",)) for c in num_cols]
+    if any(r is None for r in rows):
+        return None
+    width = max(int(r.numel()) for r in rows)
+    if any(int(r.numel()) != width for r in rows):
+        rows = [torch.nn.functional.pad(r, (0, width - int(r.numel()))) for r in rows]
+    cnt = torch.stack(rows)
+    dist.all_reduce_(cnt, "sum")
+    return cnt.cpu().numpy().tolist()
+
+
 def batched_bin_frequencies(binned_idf, cols, total: int, max_bin: int = 0):
     """Per-bin frequencies for many columns at once: numeric (binned)
     columns go through ONE fused histogram kernel + one all-reduce;
     categorical columns through the fused dictionary bincount. Pass
     ``max_bin`` (= the binning bin_size) to skip the moments pass — the
-    per-column null count then falls out of the histogram row sum."""
+    per-column null count then falls out of the histogram row sum.
+    Numeric columns that all still carry attribute_binning's count rows
+    skip both passes; the result is the same."""
     from anovos_amd.ops import histogram as hist_ops
     from anovos_amd.ops import stats as stats_ops
 
     out = {}
     num_cols = [c for c in cols if binned_idf.col(c).kind == "numerical"]
     cat_cols = [c for c in cols if c not in num_cols]
-    if num_cols:
+    cached = _cached_bin_counts(binned_idf, num_cols)
+    if cached is not None:
+        # attribute_binning's kernel already counted every bin while it
+        # wrote these columns: no pass over the binned frame at all.
+        # Row layout: slot 0 nulls, slot b = bin label b.
+        for i, c in enumerate(num_cols):
+            h = cached[i][1:]
+            if max_bin:
+                # the histogram path clamps labels above max_bin into the
+                # edge bin (pre-existing models with longer cutoff lists)
+                M = int(max_bin)
+                h = h[: M - 1] + [sum(h[M - 1 :])]
+            keys, vals = [], []
+            nnull = int(total - float(sum(h)))
+            if nnull:
+                keys.append("-1")
+                vals.append(nnull / total)
+            for b, hb in enumerate(h):
+                if hb > 0:
+                    keys.append(str(b + 1))
+                    vals.append(hb / total)
+            out[c] = (keys, vals)
+    elif num_cols:
         if max_bin:
             M = int(max_bin)
             ns = None
@@ -228,6 +272,14 @@ def _bin_frequencies(binned_idf, col: str, total: int):
         if nnull:
             keys.append("-1")
             vals.append(nnull / total)
+        return keys, vals
+    cached = _cached_bin_counts(binned_idf, [col])
+    if cached is not None:
+        keys, vals = [], []
+        for b, cb in enumerate(cached[0]):
+            if cb > 0:
+                keys.append(str(b) if b else "-1")
+                vals.append(float(cb) / total)
         return keys, vals
     t = c.data
     vals_t = torch.nan_to_num(t, nan=-1.0)

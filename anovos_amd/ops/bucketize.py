@@ -9,7 +9,7 @@ binary search per value. Torch path: torch.bucketize per column.
 
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Sequence, Tuple
 
 import torch
 
@@ -54,3 +54,30 @@ def bucketize_columns_float(tensors: Sequence[torch.Tensor], cutoffs: Sequence[t
         idx = torch.where(torch.isnan(t), torch.full_like(idx, float("nan")), idx)
         out.append(idx)
     return out
+
+
+def bucketize_columns_float_counts(
+    tensors: Sequence[torch.Tensor], cutoffs: Sequence[torch.Tensor]
+) -> Tuple[List[torch.Tensor], torch.Tensor]:
+    """bucketize_columns_float plus the per-column bin counts the same
+    pass sees: int64 [ncols, max_ncut + 2] LOCAL counts on the columns'
+    device, slot 0 = nulls, slot b = bin label b (1..ncut+1). The GPU
+    kernel counts while it writes; the torch path bincounts the produced
+    column. No host sync either way."""
+    if tensors and tensors[0].is_cuda and backend.use_hip(tensors[0]):
+        ext = backend.hip_ext()
+        # cutoffs stay where they are: the binding flattens them on the
+        # host, so a device copy would only be read back (one sync each)
+        outs, counts = ext.bucketize_columns_float_counts(
+            [t.contiguous() for t in tensors],
+            [c.to(torch.float64).contiguous() for c in cutoffs],
+        )
+        return list(outs), counts
+    outs = bucketize_columns_float(tensors, cutoffs)
+    stride = max([int(c.numel()) + 2 for c in cutoffs] + [2])
+    dev = tensors[0].device if tensors else torch.device("cpu")
+    counts = torch.zeros(len(outs), stride, dtype=torch.int64, device=dev)
+    for i, o in enumerate(outs):
+        slot = torch.nan_to_num(o, nan=0.0).to(torch.long).reshape(-1)
+        counts[i] = torch.bincount(slot, minlength=stride)
+    return outs, counts

@@ -49,6 +49,11 @@ int anovos_bucketize_float(const void *const *cols, const int64_t *lens, int nco
                            const double *cutflat, const int64_t *cutoff_off,
                            const int *cutoff_len, int max_ncut, int nchunks, int dtype,
                            float *const *outs, hipStream_t stream);
+int anovos_bucketize_float_counts(const void *const *cols, const int64_t *lens, int ncols,
+                                  const double *cutflat, const int64_t *cutoff_off,
+                                  const int *cutoff_len, int max_ncut, int nchunks, int dtype,
+                                  float *const *outs, uint64_t *counts, const int64_t *count_off,
+                                  hipStream_t stream);
 int anovos_lut_apply_f32(const int32_t *const *cols, const int64_t *lens, int ncols,
                          const float *lutflat, const int64_t *lut_off, int nchunks,
                          float *const *outs, hipStream_t stream);
@@ -587,6 +592,69 @@ std::vector<torch::Tensor> bucketize_columns_float(std::vector<torch::Tensor> co
   return outs;
 }
 
+// K6 with counts: same outputs as bucketize_columns_float plus per-column
+// bin counts from the same pass. counts is int64 [ncols, max_ncut + 2] in
+// the ORIGINAL column order (slot 0 nulls, slot b = bin label b), local to
+// this rank, left on the device.
+std::tuple<std::vector<torch::Tensor>, torch::Tensor> bucketize_columns_float_counts(
+    std::vector<torch::Tensor> cols, std::vector<torch::Tensor> cutoffs) {
+  TORCH_CHECK(!cols.empty(), "no columns");
+  TORCH_CHECK(cols.size() == cutoffs.size(), "cols/cutoffs size mismatch");
+  auto device = cols[0].device();
+  std::vector<torch::Tensor> outs;
+  int64_t stride = 2;
+  for (size_t i = 0; i < cols.size(); ++i) {
+    TORCH_CHECK(cols[i].is_contiguous() && cols[i].device() == device,
+                "columns must be contiguous, same device");
+    TORCH_CHECK(cutoffs[i].numel() <= 4096, "cutoff count out of LDS range");
+    outs.push_back(torch::empty(cols[i].sizes(), torch::TensorOptions().dtype(torch::kFloat32).device(device)));
+    stride = std::max<int64_t>(stride, cutoffs[i].numel() + 2);
+  }
+  auto counts = torch::zeros({(int64_t)cols.size(), stride},
+                             torch::TensorOptions().dtype(torch::kInt64).device(device));
+  for (int pass = 0; pass < 2; ++pass) {
+    std::vector<int64_t> ptrs, lens, optrs, offs, coffs;
+    std::vector<double> flat;
+    std::vector<int> clens;
+    int max_ncut = 1;
+    for (size_t i = 0; i < cols.size(); ++i) {
+      if (dtype_code(cols[i]) != pass) continue;
+      ptrs.push_back((int64_t)cols[i].data_ptr());
+      lens.push_back(cols[i].numel());
+      optrs.push_back((int64_t)outs[i].data_ptr());
+      coffs.push_back((int64_t)i * stride);
+      auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
+      offs.push_back((int64_t)flat.size());
+      const double *cd = cc.data_ptr<double>();
+      flat.insert(flat.end(), cd, cd + cc.numel());
+      clens.push_back((int)cc.numel());
+      max_ncut = std::max(max_ncut, (int)cc.numel());
+    }
+    if (ptrs.empty()) continue;
+    if (flat.empty()) flat.push_back(0.0);  // from_blob on empty data() segfaults
+    int ncols = (int)ptrs.size();
+    int64_t maxn = *std::max_element(lens.begin(), lens.end());
+    int nchunks = pick_chunks(maxn, ncols);
+    auto dptr = to_device_i64(ptrs, device);
+    auto dlen = to_device_i64(lens, device);
+    auto dout = to_device_i64(optrs, device);
+    auto doff = to_device_i64(offs, device);
+    auto dcoff = to_device_i64(coffs, device);
+    auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
+                                  torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
+    auto dclen = torch::from_blob(clens.data(), {(int64_t)clens.size()},
+                                  torch::TensorOptions().dtype(torch::kInt32)).clone().to(device);
+    check_hip(anovos_bucketize_float_counts(
+                  (const void *const *)dptr.data_ptr<int64_t>(), dlen.data_ptr<int64_t>(), ncols,
+                  dflat.data_ptr<double>(), doff.data_ptr<int64_t>(), dclen.data_ptr<int>(),
+                  max_ncut, nchunks, pass, (float *const *)dout.data_ptr<int64_t>(),
+                  (uint64_t *)counts.data_ptr<int64_t>(), dcoff.data_ptr<int64_t>(),
+                  current_stream()),
+              "anovos_bucketize_float_counts");
+  }
+  return {outs, counts};
+}
+
 std::vector<torch::Tensor> lut_apply_f32(std::vector<torch::Tensor> cols,
                                          std::vector<torch::Tensor> luts) {
   TORCH_CHECK(cols.size() == luts.size(), "cols/luts size mismatch");
@@ -988,6 +1056,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("centered_gram_bf16", &centered_gram_bf16, "bf16 MFMA centered Gram X^T X (K8)");
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
+  m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,
+        "bucketize to float bin labels + per-column bin counts from the same pass (K6)");
   m.def("lut_apply_f32", &lut_apply_f32, "fused LUT gather -> float (K12)");
   m.def("lut_apply_i32", &lut_apply_i32, "fused LUT gather -> int32 (K12)");
   m.def("hll_registers_multi", &hll_registers_multi, "fused multi-column HLL (K4)");

@@ -392,15 +392,69 @@ __global__ __launch_bounds__(THREADS) void bucketize_kernel(
 // float-output bucketize: writes (bin index + 1) as float32 with NaN for
 // null — exactly the binned-column layout attribute_binning materializes
 // (avoids three extra elementwise passes per column on the python side).
-template <typename T>
+//
+// COUNT variant: the same pass also accumulates per-column bin counts
+// (slot 0 = nulls, slot b = bin label b, b = 1..ncut+1) so the drift
+// frequency pass does not have to re-read the binned frame. Counts are
+// staged per block in LDS behind the cutoffs ([max_ncut] doubles, then
+// [max_ncut+2] shared u32 counters, then the optional privates) and
+// flushed with one 64-bit atomic per non-zero slot per block into
+// counts[count_off[col] + slot]. For max_ncut + 2 <= 17 (launch-uniform:
+// the launcher sizes the LDS for the whole launch) each thread owns a
+// private stride-17 counter row, as in bucketize_label_counts_kernel;
+// there is no label to pack here, so the privates are full 32-bit
+// counters and need no chunk-size overflow guard. Larger cutoff lists
+// use shared LDS atomics. The non-COUNT instantiation is unchanged.
+#define BKT_PRIV_STRIDE 17
+
+// Register-resident cutoffs for the f32 placement scans (NREG > 0, chosen
+// per launch from max_ncut: 9 covers the library-wide default bin_size=10
+// without dead compares, 16 the rest of the short lists). Each thread
+// copies the column's adjusted f32 cutoffs out of LDS once, padded with
+// +INF (a pad never satisfies cut < v, whatever v is), and the compare
+// chain is fully unrolled with static indices — the inner loop then
+// issues no LDS reads for cutoffs. Same compares as the LDS scan, so the
+// placement is bit-identical (NaN cutoffs never compare true either way).
+// NREG == 0 keeps the cutoffs in LDS.
+template <int NREG>
+struct RegCuts {
+  float c[NREG > 0 ? NREG : 1];
+  DEV_INLINE void load(const float *cutsf, int ncut) {
+#pragma unroll
+    for (int j = 0; j < NREG; ++j) c[j] = (j < ncut) ? cutsf[j] : INFINITY;
+  }
+  DEV_INLINE int below(float v) const {
+    int lo = 0;
+#pragma unroll
+    for (int j = 0; j < NREG; ++j) lo += (c[j] < v) ? 1 : 0;
+    return lo;
+  }
+};
+static int bkt_nreg(int max_ncut) { return max_ncut <= 9 ? 9 : (max_ncut <= 16 ? 16 : 0); }
+
+template <typename T, bool COUNT, int NREG>
 __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
     const T *const *cols, const int64_t *lens,
     const double *cutflat, const int64_t *cutoff_off, const int *cutoff_len,
-    int nchunks, float *const *outs) {
+    int nchunks, float *const *outs, int max_ncut, uint64_t *counts,
+    const int64_t *count_off) {
   extern __shared__ double cuts[];
   const int col = blockIdx.x / nchunks;
   const int chunk = blockIdx.x % nchunks;
   const int ncut = cutoff_len[col];
+  uint32_t *cnt = nullptr;   // [max_ncut + 2] block-shared counters
+  uint32_t *priv = nullptr;  // this thread's private row (private mode)
+  bool use_priv = false;
+  if (COUNT) {
+    cnt = reinterpret_cast<uint32_t *>(cuts + max_ncut);
+    use_priv = (max_ncut + 2 <= BKT_PRIV_STRIDE);
+    for (int i = threadIdx.x; i < max_ncut + 2; i += THREADS) cnt[i] = 0;
+    if (use_priv) {
+      uint32_t *base0 = cnt + (max_ncut + 2);
+      for (int i = threadIdx.x; i < THREADS * BKT_PRIV_STRIDE; i += THREADS) base0[i] = 0;
+      priv = base0 + (uint32_t)threadIdx.x * BKT_PRIV_STRIDE;
+    }
+  }
   const double *src = &cutflat[cutoff_off[col]];
   // f32 columns scan f32 cuts with f64-EXACT placement: for an f32
   // value v, (cut < (double)v) <=> (cutf < v) where cutf is (float)cut
@@ -419,6 +473,8 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
     for (int i = threadIdx.x; i < ncut; i += THREADS) cuts[i] = src[i];
   }
   __syncthreads();
+  RegCuts<NREG> rc;
+  if (NREG > 0) rc.load(cutsf, ncut);
   const T *__restrict__ x = cols[col];
   float *__restrict__ out = outs[col];
   const int64_t n = lens[col];
@@ -450,7 +506,9 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
   auto placef = [&](float v) -> float {
     if (isnan(v)) return nanf("");
     int lo;
-    if (ncut <= 32) {
+    if (NREG > 0) {
+      lo = rc.below(v);
+    } else if (ncut <= 32) {
       lo = 0;
       for (int j = 0; j < ncut; ++j) lo += (cutsf[j] < v) ? 1 : 0;
     } else {
@@ -464,6 +522,13 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
       }
     }
     return (float)(lo + 1);
+  };
+  // the label the placement lambdas produced names its own slot:
+  // NaN (null) -> 0, bin label b -> b (<= ncut + 1 <= max_ncut + 1)
+  auto count = [&](float r) {
+    const int slot = (r == r) ? (int)r : 0;
+    if (use_priv) priv[slot] += 1u;
+    else atomicAdd(&cnt[slot], 1u);
   };
   if (sizeof(T) == 4) {
     const int64_t nv = (e - s) / 4;
@@ -484,6 +549,10 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
       q.w = placef(w.w);
       __builtin_nontemporal_store(r, &ov[i]);
       __builtin_nontemporal_store(q, &ov[i + THREADS]);
+      if (COUNT) {
+        count(r.x); count(r.y); count(r.z); count(r.w);
+        count(q.x); count(q.y); count(q.z); count(q.w);
+      }
     }
     for (; i < nv; i += THREADS) {
       nat_f4 v = xv[i];
@@ -493,12 +562,35 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
       r.z = placef(v.z);
       r.w = placef(v.w);
       ov[i] = r;
+      if (COUNT) {
+        count(r.x); count(r.y); count(r.z); count(r.w);
+      }
     }
-    for (int64_t j = s + nv * 4 + threadIdx.x; j < e; j += THREADS)
-      out[j] = placef((float)x[j]);
+    for (int64_t j = s + nv * 4 + threadIdx.x; j < e; j += THREADS) {
+      const float r = placef((float)x[j]);
+      out[j] = r;
+      if (COUNT) count(r);
+    }
   } else {
-    for (int64_t i = s + threadIdx.x; i < e; i += THREADS)
-      out[i] = place((double)x[i]);
+    for (int64_t i = s + threadIdx.x; i < e; i += THREADS) {
+      const float r = place((double)x[i]);
+      out[i] = r;
+      if (COUNT) count(r);
+    }
+  }
+  if (COUNT) {
+    __syncthreads();
+    const int slots = ncut + 2;
+    if (use_priv) {
+      for (int s2 = 0; s2 < slots; ++s2) {
+        const uint32_t v = priv[s2];
+        if (v) atomicAdd(&cnt[s2], v);
+      }
+      __syncthreads();
+    }
+    uint64_t *g = counts + count_off[col];
+    for (int b = threadIdx.x; b < slots; b += THREADS)
+      if (cnt[b]) atomicAdd((unsigned long long *)&g[b], (unsigned long long)cnt[b]);
   }
 }
 
@@ -1072,11 +1164,44 @@ int anovos_bucketize_float(const void *const *cols, const int64_t *lens, int nco
   size_t lds = (size_t)max_ncut * 8;
   if (lds < 8) lds = 8;
   if (dtype == 0)
-    hipLaunchKernelGGL(bucketize_float_kernel<float>, grid, dim3(THREADS), lds, stream,
-                       (const float *const *)cols, lens, cutflat, cutoff_off, cutoff_len, nchunks, outs);
+    hipLaunchKernelGGL((bucketize_float_kernel<float, false, 0>), grid, dim3(THREADS), lds, stream,
+                       (const float *const *)cols, lens, cutflat, cutoff_off, cutoff_len, nchunks, outs,
+                       max_ncut, (uint64_t *)nullptr, (const int64_t *)nullptr);
   else
-    hipLaunchKernelGGL(bucketize_float_kernel<double>, grid, dim3(THREADS), lds, stream,
-                       (const double *const *)cols, lens, cutflat, cutoff_off, cutoff_len, nchunks, outs);
+    hipLaunchKernelGGL((bucketize_float_kernel<double, false, 0>), grid, dim3(THREADS), lds, stream,
+                       (const double *const *)cols, lens, cutflat, cutoff_off, cutoff_len, nchunks, outs,
+                       max_ncut, (uint64_t *)nullptr, (const int64_t *)nullptr);
+  return (int)hipGetLastError();
+}
+
+// counting variant: counts is zeroed by the caller; column c of this
+// launch owns the cutoff_len[c] + 2 slots at counts[count_off[c]], and
+// cutoff_len[c] <= max_ncut (max_ncut >= 1 sizes the LDS).
+int anovos_bucketize_float_counts(const void *const *cols, const int64_t *lens, int ncols,
+                                  const double *cutflat, const int64_t *cutoff_off,
+                                  const int *cutoff_len, int max_ncut, int nchunks, int dtype,
+                                  float *const *outs, uint64_t *counts, const int64_t *count_off,
+                                  hipStream_t stream) {
+  dim3 grid(ncols * nchunks);
+  size_t lds = (size_t)max_ncut * sizeof(double) + (size_t)(max_ncut + 2) * sizeof(uint32_t);
+  if (max_ncut + 2 <= BKT_PRIV_STRIDE)
+    lds += (size_t)THREADS * BKT_PRIV_STRIDE * sizeof(uint32_t);  // per-thread privates
+#define BKT_COUNTS_F32(NREG)                                                                        \
+  hipLaunchKernelGGL((bucketize_float_kernel<float, true, NREG>), grid, dim3(THREADS), lds, stream, \
+                     (const float *const *)cols, lens, cutflat, cutoff_off, cutoff_len, nchunks,    \
+                     outs, max_ncut, counts, count_off)
+  const int nreg = bkt_nreg(max_ncut);
+  if (dtype == 0 && nreg == 9)
+    BKT_COUNTS_F32(9);
+  else if (dtype == 0 && nreg == 16)
+    BKT_COUNTS_F32(16);
+  else if (dtype == 0)
+    BKT_COUNTS_F32(0);
+  else
+    hipLaunchKernelGGL((bucketize_float_kernel<double, true, 0>), grid, dim3(THREADS), lds, stream,
+                       (const double *const *)cols, lens, cutflat, cutoff_off, cutoff_len, nchunks, outs,
+                       max_ncut, counts, count_off);
+#undef BKT_COUNTS_F32
   return (int)hipGetLastError();
 }
 
@@ -1556,7 +1681,7 @@ extern "C" int anovos_label_counts_multi(
 // column: NaN -> 0, bin b=lo+1 -> slot b+1. Layout per column at
 // out[off]: [slots] totals then [slots] events.
 // ------------------------------------------------------------------
-template <typename T>
+template <typename T, int NREG>
 __global__ __launch_bounds__(THREADS) void bucketize_label_counts_kernel(
     const T *const *cols, const uint8_t *__restrict__ label,
     const int64_t *lens, const double *cutflat, const int64_t *cutoff_off,
@@ -1585,6 +1710,8 @@ __global__ __launch_bounds__(THREADS) void bucketize_label_counts_kernel(
   }
   for (int i = threadIdx.x; i < 2 * slots; i += THREADS) cnt[i] = 0;
   __syncthreads();
+  RegCuts<NREG> rc;  // f32 launches with max_ncut <= 16: cutoffs in registers
+  if (NREG > 0) rc.load(cutsf, ncut);
 
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
@@ -1595,7 +1722,9 @@ __global__ __launch_bounds__(THREADS) void bucketize_label_counts_kernel(
   auto slot_f32 = [&](float v) -> int {
     if (v != v) return 0;
     int lo = 0;
-    if (ncut <= 32) {
+    if (NREG > 0) {
+      lo = rc.below(v);
+    } else if (ncut <= 32) {
       for (int j = 0; j < ncut; ++j) lo += (cutsf[j] < v) ? 1 : 0;
     } else {
       int len = ncut;
@@ -1734,17 +1863,25 @@ extern "C" int anovos_bucketize_label_counts(
                (size_t)max_slots * 2 * sizeof(uint32_t);
   if (dtype == 0 && max_slots <= 16)
     lds += (size_t)THREADS * 17 * sizeof(uint32_t);  // per-thread privates
-  if (dtype == 0)
-    hipLaunchKernelGGL(bucketize_label_counts_kernel<float>,
-                       dim3(ncols * nchunks), dim3(THREADS), lds, stream,
-                       (const float *const *)cols, label, lens, cutflat,
-                       cutoff_off, cutoff_len, offs, sizes, max_ncut, max_slots,
-                       nchunks, out);
+#define BKT_LABEL_F32(NREG)                                                     \
+  hipLaunchKernelGGL((bucketize_label_counts_kernel<float, NREG>),              \
+                     dim3(ncols * nchunks), dim3(THREADS), lds, stream,         \
+                     (const float *const *)cols, label, lens, cutflat,          \
+                     cutoff_off, cutoff_len, offs, sizes, max_ncut, max_slots,  \
+                     nchunks, out)
+  const int nreg = bkt_nreg(max_ncut);
+  if (dtype == 0 && nreg == 9)
+    BKT_LABEL_F32(9);
+  else if (dtype == 0 && nreg == 16)
+    BKT_LABEL_F32(16);
+  else if (dtype == 0)
+    BKT_LABEL_F32(0);
   else
-    hipLaunchKernelGGL(bucketize_label_counts_kernel<double>,
+    hipLaunchKernelGGL((bucketize_label_counts_kernel<double, 0>),
                        dim3(ncols * nchunks), dim3(THREADS), lds, stream,
                        (const double *const *)cols, label, lens, cutflat,
                        cutoff_off, cutoff_len, offs, sizes, max_ncut, max_slots,
                        nchunks, out);
+#undef BKT_LABEL_F32
   return (int)hipGetLastError();
 }

@@ -70,23 +70,31 @@ def _exact_integral_quantiles(idf, cols, probs, moments):
 
     import numpy as np
 
-    R = [int(moments[c].max - moments[c].min) + 1 for c in cols]
-    M = max(R)
-    lo = torch.tensor([moments[c].min - 0.5 for c in cols], dtype=torch.float64)
-    hi = torch.tensor([moments[c].min - 0.5 + M for c in cols], dtype=torch.float64)
-    h = global_histograms([idf.col(c).data for c in cols], lo, hi, M).cpu().numpy()
+    R = {c: int(moments[c].max - moments[c].min) + 1 for c in cols}
+    # a column whose dense counts are already cached (an earlier call with
+    # other probabilities) is not read again
+    cold = [c for c in cols if ("inthist",) not in idf.col(c).cache]
+    if cold:
+        M = max(R[c] for c in cold)
+        lo = torch.tensor([moments[c].min - 0.5 for c in cold], dtype=torch.float64)
+        hi = torch.tensor([moments[c].min - 0.5 + M for c in cold], dtype=torch.float64)
+        h = global_histograms([idf.col(c).data for c in cold], lo, hi, M).cpu().numpy()
+        for i, c in enumerate(cold):
+            # the dense per-integer counts serve discrete_modes too — one
+            # frame read covers exact quantiles AND exact modes
+            idf.col(c).cache[("inthist",)] = (h[i][: R[c]].copy(), float(moments[c].min))
     out = {}
-    for i, c in enumerate(cols):
+    for c in cols:
         n = int(moments[c].n)
-        # the dense per-integer counts serve discrete_modes too — one
-        # frame read covers exact quantiles AND exact modes
-        idf.col(c).cache[("inthist",)] = (h[i][: R[i]].copy(), float(moments[c].min))
-        cdf = np.cumsum(h[i])
+        counts, cmin = idf.col(c).cache[("inthist",)]
+        # every value lies in [min, max], so the counts past R are zero and
+        # the truncated CDF gives the same first-reaching index
+        cdf = np.cumsum(counts)
         vals = []
         for p in probs:
             r = min(max(int(_math.ceil(p * n)), 1), n)
             b = int(np.searchsorted(cdf, r, side="left"))
-            vals.append(float(moments[c].min + min(b, R[i] - 1)))
+            vals.append(float(cmin + min(b, R[c] - 1)))
         out[c] = vals
     return out
 
