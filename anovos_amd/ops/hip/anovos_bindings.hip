@@ -65,7 +65,7 @@ int anovos_fill_code(const int32_t *const *cols, const int64_t *lens, int ncols,
                      hipStream_t stream);
 int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
                              const int64_t *offs, const int *sizes, int ncols,
-                             int max_slots, int nchunks, uint64_t *out,
+                             int lds_slots, int nchunks, uint64_t *out,
                              hipStream_t stream);
 int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
                          int ncols, const double *lo, const double *hi,
@@ -140,6 +140,15 @@ int dtype_code(const torch::Tensor &t) {
   return -1;
 }
 
+// Every kernel reads a column as a dense array from data_ptr(): a strided
+// view would be read as if dense, a tensor on another device not at all.
+void check_cols(const std::vector<torch::Tensor> &cols, const torch::Device &device,
+                const char *what) {
+  for (auto &t : cols)
+    TORCH_CHECK(t.is_contiguous() && t.device() == device, what,
+                ": columns must be contiguous, same device");
+}
+
 }  // namespace
 
 torch::Tensor column_moments(std::vector<torch::Tensor> cols, std::vector<double> shifts) {
@@ -187,6 +196,7 @@ torch::Tensor column_histograms(std::vector<torch::Tensor> cols, torch::Tensor l
                                 torch::Tensor hi, int64_t nbins) {
   TORCH_CHECK(!cols.empty(), "no columns");
   auto device = cols[0].device();
+  check_cols(cols, device, "column_histograms");
   auto lo_d = lo.to(torch::kFloat64).to(device);
   auto hi_d = hi.to(torch::kFloat64).to(device);
   auto out = torch::zeros({(int64_t)cols.size(), nbins},
@@ -223,6 +233,7 @@ torch::Tensor bracket_histograms(std::vector<torch::Tensor> cols, torch::Tensor 
                                  torch::Tensor lo, torch::Tensor hi, int64_t nbins) {
   TORCH_CHECK(!cols.empty(), "no columns");
   auto device = cols[0].device();
+  check_cols(cols, device, "bracket_histograms");
   int dtype = dtype_code(cols[0]);
   for (auto &t : cols) TORCH_CHECK(dtype_code(t) == dtype, "bracket_histograms: mixed dtypes unsupported");
   std::vector<int64_t> ptrs, lens;
@@ -252,6 +263,7 @@ std::vector<torch::Tensor> bucketize_columns(std::vector<torch::Tensor> cols,
                                              std::vector<torch::Tensor> cutoffs) {
   TORCH_CHECK(cols.size() == cutoffs.size(), "cols/cutoffs size mismatch");
   auto device = cols[0].device();
+  check_cols(cols, device, "bucketize_columns");
   std::vector<torch::Tensor> outs;
   for (auto &t : cols)
     outs.push_back(torch::empty_like(t, torch::TensorOptions().dtype(torch::kInt32).device(device)));
@@ -316,6 +328,7 @@ torch::Tensor code_counts(torch::Tensor codes, int64_t size) {
 
 torch::Tensor hll_registers(torch::Tensor x, int64_t p) {
   auto device = x.device();
+  check_cols({x}, device, "hll_registers");
   auto regs = torch::zeros({(int64_t)1 << p},
                            torch::TensorOptions().dtype(torch::kInt32).device(device));
   if (x.numel() == 0) return regs;
@@ -352,6 +365,7 @@ void row_null_counts_num(std::vector<torch::Tensor> cols, torch::Tensor out) {
 torch::Tensor hll_registers_multi(std::vector<torch::Tensor> cols, int64_t p) {
   TORCH_CHECK(!cols.empty(), "no columns");
   auto device = cols[0].device();
+  check_cols(cols, device, "hll_registers_multi");
   auto regs = torch::zeros({(int64_t)cols.size(), (int64_t)1 << p},
                            torch::TensorOptions().dtype(torch::kInt32).device(device));
   for (int pass = 0; pass < 2; ++pass) {
@@ -383,6 +397,7 @@ std::vector<torch::Tensor> scale_columns(std::vector<torch::Tensor> cols,
                                          torch::Tensor a, torch::Tensor b) {
   TORCH_CHECK(!cols.empty(), "no columns");
   auto device = cols[0].device();
+  check_cols(cols, device, "scale_columns");
   auto a_c = a.to(torch::kFloat64).cpu().contiguous();
   auto b_c = b.to(torch::kFloat64).cpu().contiguous();
   std::vector<torch::Tensor> outs;
@@ -419,6 +434,7 @@ std::vector<torch::Tensor> scale_columns(std::vector<torch::Tensor> cols,
 std::vector<torch::Tensor> fill_nan_columns(std::vector<torch::Tensor> cols, torch::Tensor fill) {
   TORCH_CHECK(!cols.empty(), "no columns");
   auto device = cols[0].device();
+  check_cols(cols, device, "fill_nan_columns");
   auto f_c = fill.to(torch::kFloat64).cpu().contiguous();
   std::vector<torch::Tensor> outs;
   for (auto &t : cols) outs.push_back(torch::empty_like(t));
@@ -489,6 +505,7 @@ torch::Tensor bracket_histograms_grouped(std::vector<torch::Tensor> cols,
   // brackets MUST be sorted by column index; returns [nbrackets, 512].
   TORCH_CHECK(!cols.empty(), "no columns");
   auto device = cols[0].device();
+  check_cols(cols, device, "bracket_histograms_grouped");
   auto bc = bracket_col.to(torch::kInt64).cpu().contiguous();
   // dtype uniformity only matters for REFERENCED columns (the host
   // splits mixed-dtype bracket sets into per-dtype launches; columns
@@ -549,6 +566,7 @@ std::vector<torch::Tensor> bucketize_columns_float(std::vector<torch::Tensor> co
                                                    std::vector<torch::Tensor> cutoffs) {
   TORCH_CHECK(cols.size() == cutoffs.size(), "cols/cutoffs size mismatch");
   auto device = cols[0].device();
+  check_cols(cols, device, "bucketize_columns_float");
   std::vector<torch::Tensor> outs;
   for (auto &t : cols)
     outs.push_back(torch::empty(t.sizes(), torch::TensorOptions().dtype(torch::kFloat32).device(device)));
@@ -659,6 +677,7 @@ std::vector<torch::Tensor> lut_apply_f32(std::vector<torch::Tensor> cols,
                                          std::vector<torch::Tensor> luts) {
   TORCH_CHECK(cols.size() == luts.size(), "cols/luts size mismatch");
   auto device = cols[0].device();
+  check_cols(cols, device, "lut_apply_f32");
   std::vector<int64_t> ptrs, lens, optrs, offs;
   std::vector<float> flat;
   std::vector<torch::Tensor> outs;
@@ -693,6 +712,7 @@ std::vector<torch::Tensor> lut_apply_i32(std::vector<torch::Tensor> cols,
                                          std::vector<torch::Tensor> luts) {
   TORCH_CHECK(cols.size() == luts.size(), "cols/luts size mismatch");
   auto device = cols[0].device();
+  check_cols(cols, device, "lut_apply_i32");
   std::vector<int64_t> ptrs, lens, optrs, offs;
   std::vector<int32_t> flat;
   std::vector<torch::Tensor> outs;
@@ -796,17 +816,22 @@ torch::Tensor code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int
   std::vector<int64_t> ptrs, lens, offs;
   std::vector<int64_t> sz64;
   int64_t off = 0, maxn = 0;
-  int max_slots = 0;
+  // the kernel stages a column's counters in LDS when its slots (codes +
+  // null slot) number <= 16384 and counts in global memory otherwise, per
+  // column: size the LDS for the largest column that stages, not for the
+  // largest column of the launch
+  int lds_slots = 0;
   for (size_t i = 0; i < cols.size(); ++i) {
     auto &t = cols[i];
     TORCH_CHECK(t.is_contiguous() && t.scalar_type() == torch::kInt32, "int32 code columns required");
+    TORCH_CHECK(sizes[i] >= 0 && sizes[i] < INT32_MAX, "dictionary size out of range");
     ptrs.push_back((int64_t)t.data_ptr());
     lens.push_back(t.numel());
     maxn = std::max(maxn, t.numel());
     offs.push_back(off);
     off += sizes[i] + 1;
     sz64.push_back(sizes[i]);
-    max_slots = std::max(max_slots, (int)sizes[i] + 1);
+    if (sizes[i] + 1 <= 16384) lds_slots = std::max(lds_slots, (int)sizes[i] + 1);
   }
   int ncols = (int)cols.size();
   int nchunks = pick_chunks(maxn, ncols);
@@ -817,7 +842,7 @@ torch::Tensor code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int
   auto dsz = to_device_i64(sz64, device).to(torch::kInt32);
   check_hip(anovos_code_counts_multi((const int32_t *const *)dptr.data_ptr<int64_t>(),
                                      dlen.data_ptr<int64_t>(), doff.data_ptr<int64_t>(),
-                                     dsz.data_ptr<int>(), ncols, max_slots, nchunks,
+                                     dsz.data_ptr<int>(), ncols, lds_slots, nchunks,
                                      (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
             "anovos_code_counts_multi");
   return out;

@@ -202,9 +202,11 @@ __global__ __launch_bounds__(THREADS) void hist_kernel(
     const double scale = (double)nbins / (h - l);
     auto body = [&](double v) {
       if (!isnan(v)) {
-        int b = (int)((v - l) * scale);
-        b = max(0, min(nbins - 1, b));
-        atomicAdd(&bins[b], 1u);
+        // clamp in fp64 BEFORE the conversion: +-inf and values far
+        // outside [l, h] must land in the edge bins without relying on
+        // how an out-of-range double converts to int
+        const double t = fmin(fmax((v - l) * scale, 0.0), (double)(nbins - 1));
+        atomicAdd(&bins[(int)t], 1u);
       }
     };
     if (sizeof(T) == 4) {
@@ -317,8 +319,8 @@ __global__ __launch_bounds__(THREADS) void bracket_hist_grouped_kernel(
 
   auto body = [&](double v) {
     if (isnan(v)) return;
-    int b1 = (int)((v - l1) * sc1);
-    b1 = max(0, min(p1bins - 1, b1));
+    // fp64 clamp before the conversion, as in hist_kernel (+-inf data)
+    const int b1 = (int)fmin(fmax((v - l1) * sc1, 0.0), (double)(p1bins - 1));
     int br = lut[b1];
     if (br >= 0 && v >= slo[br] && v < shi[br]) {
       int bin = (int)((v - slo[br]) * sscale[br]);
@@ -1481,9 +1483,12 @@ extern "C" {
 
 int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
                              const int64_t *offs, const int *sizes, int ncols,
-                             int max_slots, int nchunks, uint64_t *out,
+                             int lds_slots, int nchunks, uint64_t *out,
                              hipStream_t stream) {
-  size_t lds = (max_slots <= 16384) ? (size_t)max_slots * 4 : 0;
+  // lds_slots: the most slots (sizes[c] + 1) among the columns that stage
+  // their counters in LDS (<= 16384 slots); 0 when none does
+  if (lds_slots < 0 || lds_slots > 16384) return (int)hipErrorInvalidValue;
+  size_t lds = (size_t)lds_slots * 4;
   hipLaunchKernelGGL(code_counts_multi_kernel, dim3(ncols * nchunks),
                      dim3(THREADS), lds, stream, cols, lens, offs, sizes,
                      nchunks, out);
@@ -1589,6 +1594,18 @@ extern "C" int anovos_moments_hll(const void *const *cols, const int64_t *lens,
 // v -> trunc(v)+1, clamped — matches the host torch fallback exactly);
 // 1 = int32 dictionary codes (null/invalid -> last slot).
 // ------------------------------------------------------------------
+// f32 binned value -> slot: NaN -> 0, v -> trunc(v) + 1 clamped to
+// [0, slots - 1]. The clamp is done in fp32 before the conversion: for
+// v >= 2^31 (1e30, +inf) the converted int saturates at INT_MAX and a
+// + 1 after it is a signed overflow (undefined; wrapped, it names slot 0
+// where the top slot is meant). Clamping to [-1, slots - 1] leaves every
+// in-range value's truncation unchanged (slots <= 8192 is exact in fp32).
+DEV_INLINE int label_slot_f32(float v, int slots) {
+  if (v != v) return 0;
+  const int slot = (int)fminf(fmaxf(v, -1.0f), (float)(slots - 1)) + 1;
+  return (slot >= slots) ? slots - 1 : slot;
+}
+
 __global__ __launch_bounds__(THREADS) void label_counts_multi_kernel(
     const void *const *cols, const uint8_t *__restrict__ label,
     const int64_t *lens, const int64_t *offs, const int *sizes,
@@ -1616,16 +1633,13 @@ __global__ __launch_bounds__(THREADS) void label_counts_multi_kernel(
       float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        int slot = (vv[k] != vv[k]) ? 0 : (int)vv[k] + 1;
-        slot = (slot < 0) ? 0 : ((slot >= slots) ? slots - 1 : slot);
+        const int slot = label_slot_f32(vv[k], slots);
         atomicAdd(&tot[slot], 1u);
         if (label[r + k]) atomicAdd(&evt[slot], 1u);
       }
     }
     for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += THREADS) {
-      float v = x[i];
-      int slot = (v != v) ? 0 : (int)v + 1;
-      slot = (slot < 0) ? 0 : ((slot >= slots) ? slots - 1 : slot);
+      const int slot = label_slot_f32(x[i], slots);
       atomicAdd(&tot[slot], 1u);
       if (label[i]) atomicAdd(&evt[slot], 1u);
     }

@@ -121,10 +121,13 @@ def column_histograms(
         x = t[~torch.isnan(t)].to(torch.float64)
         l, h = float(lo[i]), float(hi[i])
         if x.numel() == 0 or not (h > l):
-            if x.numel() and h == l:
-                out[i, 0] = x.numel()
+            # no usable range (constant column, or hi < lo): every
+            # non-null value counts in bin 0, as in the kernel
+            out[i, 0] = x.numel()
             continue
-        idx = ((x - l) * (nbins / (h - l))).long().clamp_(0, nbins - 1)
+        # clamp in floating point first, as the kernel does: .long() of
+        # +-inf is not defined (it put +inf into bin 0)
+        idx = ((x - l) * (nbins / (h - l))).clamp_(0, nbins - 1).long()
         out[i] = torch.bincount(idx, minlength=nbins)
     return out
 
