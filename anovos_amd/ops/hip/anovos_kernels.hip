@@ -305,10 +305,14 @@ __global__ __launch_bounds__(THREADS) void bracket_hist_grouped_kernel(
     shi[threadIdx.x] = bh;
     double w = bh - bl;
     sscale[threadIdx.x] = (w > 0) ? (double)RB_BINS / w : 0.0;
-    // floor with epsilon: grid-aligned bl maps exactly; a sub-bin
-    // bracket (refine >= 2) maps to the bin that CONTAINS it
-    int bin1 = (int)((bl - l1) * sc1 + 1e-6);
-    if (bin1 >= 0 && bin1 < p1bins) lut[bin1] = (int16_t)threadIdx.x;
+    // pass-1 bin of the bracket's MIDPOINT, computed exactly as the
+    // elements compute theirs below: a point inside the bracket lies in
+    // the cell that contains it at any depth (a bracket at the top of a
+    // cell, narrower than any fixed epsilon, must not map to the next
+    // cell). ops.histogram._refine_pass groups launches by the same rule.
+    const double mid = (bl + bh) * 0.5;
+    const int bin1 = (int)fmin(fmax((mid - l1) * sc1, 0.0), (double)(p1bins - 1));
+    if (w > 0) lut[bin1] = (int16_t)threadIdx.x;
   }
   __syncthreads();
   const T *__restrict__ x = cols[col];

@@ -4,12 +4,15 @@ Replaces Spark's Greenwald-Khanna `approxQuantile` (rel-err 0.01,
 reference stats_generator.py:906-908, quality_checker.py:843-847,
 transformers.py:210-215). Algorithm: fused equal-width histogram over all
 columns in one kernel (LDS-staged bins on GPU), all-reduced across ranks,
-then an ADAPTIVE per-quantile bracket refinement pass (LUT-grouped, one
-column read serves all of a column's brackets) that only runs while a
-bracket's rank mass exceeds the rel-err tolerance — at production row
-counts the 2048-bin pass-1 CDF already satisfies Spark's 1% band, and a
-second pass reaches rank resolution nbins*512 (≈1e6) when asked for
-tighter rel_err.
+then ADAPTIVE per-quantile bracket refinement passes (LUT-grouped, one
+column read serves all of a column's brackets) that run while a bracket's
+rank mass exceeds the rel-err tolerance — at production row counts the
+2048-bin pass-1 CDF already satisfies Spark's 1% band for smooth columns,
+and each further pass narrows a bracket 512x. Only the columns of
+unresolved brackets are read again. A bracket whose mass does not split
+is cut to the span of its data (a masked min/max); a single value — a
+spike — is the answer itself. Columns holding +-inf, and the rare column
+that stays unresolved, are sorted.
 """
 
 from __future__ import annotations
@@ -23,6 +26,57 @@ from anovos_amd.ops import backend
 
 DEFAULT_BINS = 2048
 EXACT_N_THRESHOLD = 250_000  # below this, sort-exact quantiles (GK parity)
+# Bound on refinement passes. One pass narrows a bracket 512x (2048x on the
+# CPU) and a bracket whose mass does not split is cut to the span of its
+# data, so a handful of passes serve any dynamic range; a column that is
+# still unresolved after them is sorted.
+MAX_REFINE_PASSES = 8
+# A bracket narrower than this many ulps of its bounds is not split again:
+# its sub-bin bounds (width / 2048 at the finest) would no longer be
+# distinct doubles. An f32 ulp is 2^29 f64 ulps, so f32 values still
+# separate long before this.
+_MIN_SPLIT_ULPS = 4 * 2048
+
+
+def _splittable(bracket):
+    import numpy as np
+
+    bl, bh = bracket[0], bracket[1]
+    return bh - bl > _MIN_SPLIT_ULPS * float(np.spacing(max(abs(bl), abs(bh))))
+
+
+def _bracket_extrema(tensors, brackets):
+    """(min, max) of the column's values inside [bl, bh) for each bracket
+    {(col, prob): (bl, bh, off, cnt)} — a masked reduction over the column,
+    used only for brackets whose mass does not split. Returns (inf, -inf)
+    when the range does not hold exactly the `cnt` values the histograms
+    counted for it, so a caller never resolves to a value of other rows."""
+    inf = float("inf")
+    uniq = {}
+    for k, v in brackets.items():
+        uniq.setdefault((k[0], v[0], v[1]), len(uniq))
+    dev = tensors[0].device
+    red = torch.empty(3, len(uniq), dtype=torch.float64, device=dev)
+    red[0], red[1], red[2] = inf, -inf, 0.0
+    x64, x64_col = None, None
+    for (i, bl, bh), u in sorted(uniq.items()):  # column-major: one fp64 copy per column
+        if tensors[i].numel() == 0:
+            continue
+        if x64_col != i:
+            x64, x64_col = tensors[i].to(torch.float64), i
+        m = (x64 >= bl) & (x64 < bh)  # NaN compares false
+        red[0, u] = torch.where(m, x64, torch.full_like(x64, inf)).min()
+        red[1, u] = torch.where(m, x64, torch.full_like(x64, -inf)).max()
+        red[2, u] = m.sum()
+    dist.all_reduce_(red[0], "min")
+    dist.all_reduce_(red[1], "max")
+    dist.all_reduce_(red[2], "sum")
+    red = red.cpu().tolist()
+    out = {}
+    for k, v in brackets.items():
+        u = uniq[(k[0], v[0], v[1])]
+        out[k] = (red[0][u], red[1][u]) if red[2][u] == v[3] else (inf, -inf)
+    return out
 
 
 def _exact_quantiles(idf, cols, probs, moments, rel_err=1e-4):
@@ -143,7 +197,7 @@ def approx_quantiles(
     cols: List[str],
     probs: Sequence[float],
     nbins: int = DEFAULT_BINS,
-    refine: int = 1,
+    refine: Optional[int] = None,
     moments: Optional[dict] = None,
     rel_err: float = 1e-2,
 ) -> Dict[str, List[float]]:
@@ -151,11 +205,17 @@ def approx_quantiles(
 
     Semantics follow Spark approxQuantile (default rel-err 0.01 — the
     reference's summary()/approxQuantile contract): returns a value whose
-    rank is within rel_err*n of prob*n. The adaptive refinement pass only
-    runs for brackets whose pass-1 bin still exceeds the rank tolerance
-    (at production row counts the 2048-bin pass-1 CDF already satisfies
-    0.01); pass a smaller rel_err for tighter interpolation.
+    rank is within rel_err*n of prob*n. Refinement passes run only for
+    brackets that still exceed the rank tolerance (at production row
+    counts the 2048-bin pass-1 CDF already satisfies 0.01 for smooth
+    columns) and only re-read the columns of those brackets; they repeat
+    until every bracket meets the tolerance, at most `refine` times
+    (default MAX_REFINE_PASSES). A bracket whose mass will not split — a
+    spike — resolves to the data value itself, and a column that cannot
+    be resolved this way, or whose min or max is infinite, is sorted.
     """
+    import math as _math
+
     from anovos_amd.ops import stats as stats_ops
 
     if moments is None:
@@ -170,7 +230,19 @@ def approx_quantiles(
     probs_l = list(probs)
     if all(all(("q", p) in idf.col(c).cache for p in probs_l) for c in cols):
         return {c: [idf.col(c).cache[("q", p)] for p in probs_l] for c in cols}
-    dev = idf.device
+    # a column that holds +-inf has no finite range to bin over; such
+    # columns are rare and are sorted
+    inf_cols = [c for c in cols if _math.isinf(moments[c].min) or _math.isinf(moments[c].max)]
+    if inf_cols:
+        out = _exact_quantiles(idf, inf_cols, probs_l, moments, rel_err=rel_err)
+        for c in inf_cols:
+            for j, p in enumerate(probs_l):
+                idf.col(c).cache[("q", p)] = out[c][j]
+        rest = [c for c in cols if c not in set(inf_cols)]
+        if rest:
+            out.update(approx_quantiles(idf, rest, probs_l, nbins=nbins, refine=refine,
+                                        moments=moments, rel_err=rel_err))
+        return {c: out[c] for c in cols}
     # integral columns with bounded range: EXACT quantiles from one
     # dense integer-aligned histogram (the generic 2048-bin pass-1 puts
     # each integer in a spike bin that always exceeds the rank tolerance
@@ -219,6 +291,7 @@ def approx_quantiles(
     # vectorized over the (col x prob) grid (the per-pair python loop
     # cost ~5 ms/step at 150x9)
     brackets = {}
+    top = set()  # brackets on the last pass-1 bin
     probs_np = np.asarray(probs)
     K, P = len(cols), len(probs)
     ns = np.array([moments[c].n for c in cols], dtype=np.float64)
@@ -244,27 +317,81 @@ def approx_quantiles(
             for j in range(P):
                 b = int(bs[a, j])
                 brackets[(int(i), j)] = (l + b * wa, l + (b + 1) * wa, float(targets[a, j] - belows[a, j]), float(cnts[a, j]))
-    for _ in range(refine):
-        # adaptive: only brackets whose bin still holds > rel_err/2 of the
-        # rank mass need another pass (Spark guarantees 1% rank error;
-        # within-bin interpolation already bounds ours by bin_count/n)
+        top = {(int(active[a]), int(j)) for a, j in zip(*np.nonzero(bs == nbins - 1))}
+    # adaptive: a bracket is refined while it holds > rel_err/2 of the rank
+    # mass (any point of a bracket is within its count of the target rank,
+    # so at that size the contract holds with half the tolerance to spare)
+    thr = {int(i): rel_err * 0.5 * max(ns[i], 1.0) for i in active}
+    point = {}  # (col, prob) -> data value a spike bracket resolved to
+    unresolved = set()  # columns that go to the exact sort
+    passes = MAX_REFINE_PASSES if refine is None else refine
+    over = True  # some bracket is still above the refinement threshold
+    for it in range(passes):
         need = {
-            k: v
-            for k, v in brackets.items()
-            if v[3] > rel_err * 0.5 * max(moments[cols[k[0]]].n, 1)
+            k: v for k, v in brackets.items()
+            if v[3] > thr[k[0]] and k not in point and k[0] not in unresolved
         }
+        over = bool(need)
+        need = {k: v for k, v in need.items() if _splittable(v)}
         if not need:
             break
+        if it == 0:
+            # the pass-1 histogram clamps the column maximum into its last
+            # bin; that bin's bracket is half-open, so it ends just above
+            # the maximum (children inherit the bound exactly)
+            for k in need:
+                if k in top:
+                    need[k] = (need[k][0], float(np.nextafter(highs[k[0]], np.inf))) + need[k][2:]
         refined = _refine_pass(tensors, cols, need, nbins, lo, hi)
-        brackets.update(refined)
+        stuck = {}
+        for k, v in refined.items():
+            if v[4] != need[k][3]:
+                # the sub-histogram does not hold what its parent counted
+                # (values within rounding of a bracket bound): the ranks
+                # below are no longer known, so the column is sorted
+                unresolved.add(k[0])
+            elif v[3] == need[k][3]:
+                stuck[k] = need[k]  # nothing split off: a spike, or a bracket far wider than its data
+            brackets[k] = v[:4]
+        stuck = {k: v for k, v in stuck.items() if k[0] not in unresolved}
+        if stuck:
+            # shrink a bracket whose mass did not split to the span of the
+            # values in it; a single value is the answer itself
+            for k, (mn, mx) in _bracket_extrema(tensors, stuck).items():
+                if not mn <= mx:
+                    unresolved.add(k[0])
+                elif mn == mx:
+                    point[k] = mn
+                else:
+                    brackets[k] = (mn, float(np.nextafter(mx, np.inf))) + stuck[k][2:]
+    # still above the tolerance (out of passes, or at the floating-point
+    # resolution of the bounds): a single value resolves to itself,
+    # anything else sends the column to the exact sort
+    left = {
+        k: v for k, v in brackets.items()
+        if v[3] > 2.0 * thr[k[0]] and k not in point and k[0] not in unresolved
+    } if over else {}
+    if left:
+        for k, (mn, mx) in _bracket_extrema(tensors, left).items():
+            if mn == mx:
+                point[k] = mn
+            else:
+                unresolved.add(k[0])
     for (i, j), (bl, bh, off, cnt) in brackets.items():
         c = cols[i]
-        if cnt <= 1 or bh - bl < 1e-12 * max(1.0, abs(bl)):
+        if cnt <= 1 or bh <= bl:
             result[c][j] = bl
         else:
             # interpolate inside the (now tiny) bracket by rank fraction
             frac = min(max(off / max(cnt - 1, 1e-9), 0.0), 1.0) if cnt > 1 else 0.0
             result[c][j] = bl + frac * (bh - bl)
+    for (i, j), v in point.items():
+        result[cols[i]][j] = v
+    for i, j in top:
+        # the last pass-1 bin's upper bound may round to just above the maximum
+        result[cols[i]][j] = min(result[cols[i]][j], float(highs[i]))
+    if unresolved:
+        result.update(_exact_quantiles(idf, [cols[i] for i in sorted(unresolved)], probs, moments, rel_err=rel_err))
     for c in cols:
         for j, p in enumerate(probs_l):
             idf.col(c).cache[("q", p)] = result[c][j]
@@ -276,7 +403,11 @@ def _refine_pass(tensors, cols, brackets, nbins, col_lo=None, col_hi=None):
     kernel launch reads every column once and serves all of its brackets
     (512 sub-bins, rank resolution nbins*512 per pass); brackets sit on
     the pass-1 bin grid, so the kernel resolves an element's bracket via
-    a pass-1-bin LUT in O(1). CPU: torch loop."""
+    a pass-1-bin LUT in O(1). CPU: torch loop.
+
+    Returns {key: (lo, hi, off, cnt, total)}: the sub-bin that holds the
+    key's rank, and the total of the bracket's sub-histogram, which equals
+    the parent's count unless values were lost at a bracket bound."""
     if not brackets:
         return brackets
     all_keys = sorted(brackets.keys())  # sorted by (col, prob) — grouped kernel needs col-major
@@ -323,7 +454,9 @@ def _refine_pass(tensors, cols, brackets, nbins, col_lo=None, col_hi=None):
             if degenerate:
                 bin1 = 0
             else:
-                bin1 = int((float(blo[kk]) - float(p1lo[ci])) * float(p1scale[ci]) + 1e-6)
+                # the kernel's rule: pass-1 bin of the bracket's midpoint
+                mid = (float(blo[kk]) + float(bhi[kk])) * 0.5
+                bin1 = int(min(max((mid - float(p1lo[ci])) * float(p1scale[ci]), 0.0), float(p1bins - 1)))
             placed = False
             for gi, g in enumerate(groups):
                 bins_here = seen[gi].setdefault(ci, set())
@@ -365,13 +498,14 @@ def _refine_pass(tensors, cols, brackets, nbins, col_lo=None, col_hi=None):
             xv = x[m]
             if xv.numel() == 0:
                 continue
-            idx = ((xv - l) * (nbins / (hh - l))).long().clamp_(0, nbins - 1)
+            idx = ((xv - l) * (nbins / (hh - l))).clamp_(0, nbins - 1).long()
             h[kk] = torch.bincount(idx, minlength=nbins)
     dist.all_reduce_(h, "sum")
     import numpy as np
 
     h_np = h.cpu().numpy().astype(np.float64)
     cdf = np.cumsum(h_np, axis=1)
+    totals = cdf[:, -1]
     # resolve EVERY original (col, prob) key against its (possibly
     # shared) bracket histogram — off differs per prob even when the
     # range is shared
@@ -385,10 +519,13 @@ def _refine_pass(tensors, cols, brackets, nbins, col_lo=None, col_hi=None):
     ws = (bhs - bls) / nbins
     out = {}
     for kk, k in enumerate(all_keys):
-        if bhs[kk] <= bls[kk]:
-            out[k] = brackets[k]
+        if not bhs[kk] > bls[kk]:
+            out[k] = tuple(brackets[k][:4]) + (0.0,)
             continue
         b = int(bs[kk])
-        out[k] = (bls[kk] + b * ws[kk], bls[kk] + (b + 1) * ws[kk],
-                  float(offs[kk] - belows[kk]), float(h_np[urow[kk], b]))
+        # the last sub-bin ends on the bracket's own bound, so nested
+        # brackets tile their parent without a rounding gap at the top
+        sub_hi = bhs[kk] if b == nbins - 1 else bls[kk] + (b + 1) * ws[kk]
+        out[k] = (float(bls[kk] + b * ws[kk]), float(sub_hi),
+                  float(offs[kk] - belows[kk]), float(h_np[urow[kk], b]), float(totals[urow[kk]]))
     return out

@@ -397,6 +397,73 @@ def test_bracket_histograms_grouped_edges(ext, fine_cols, dtype, p1bins):
     assert torch.equal(one[0], got[-1])
 
 
+SUB_CELLS = [0, 8, 15]  # first, a middle and the last cell of the 16-cell grid
+SUB_DEPTHS = [1, 2, 3]
+
+
+def _sub_cell_bracket(cell, depth, top):
+    """[lo, hi) of width 8 / 512^depth at the bottom or the top of a cell of
+    the 16-cell grid over [-64, 64]; every bound is an exact double."""
+    w = 8.0 / 512 ** depth
+    start = -64.0 + 8.0 * cell
+    lo = start + 8.0 - w if top else start
+    return lo, lo + w
+
+
+@pytest.fixture(scope="module")
+def sub_cell_column():
+    """One f64 column that holds, for every (cell, depth, bottom/top)
+    bracket, one value per sub-bin (lo + j * width / 512; for the depth-3
+    bracket at the top of the cell ending at 8k these are 8k - j * 2^-33,
+    j = 1..512) and values just outside both bounds, hi itself among them;
+    shuffled into 2^16 background values and NaNs, which makes two chunks
+    with an unaligned boundary. The smallest step, 2^-35, is far above the
+    ulp of 64 (2^-46), so every value is exact."""
+    g = torch.Generator().manual_seed(53)
+    parts = [_grid_data(65_536, g, torch.float64, 64)]
+    for cell in SUB_CELLS:
+        for depth in SUB_DEPTHS:
+            for top in (False, True):
+                lo, hi = _sub_cell_bracket(cell, depth, top)
+                sub = (hi - lo) / 512
+                assert sub == 2.0 ** (3 - 9 * (depth + 1))
+                inside = lo + torch.arange(512, dtype=torch.float64) * sub
+                outside = torch.tensor([lo - sub, lo - sub / 4, hi, hi + sub / 4, hi + sub], dtype=torch.float64)
+                parts += [inside, outside]
+    x = torch.cat(parts)
+    x = x[torch.randperm(x.numel(), generator=g)]
+    assert x.numel() > 65_536
+    return x, _dev(x)
+
+
+@requires_gpu
+@pytest.mark.gpu
+@pytest.mark.parametrize("top", [False, True], ids=["bottom", "top"])
+@pytest.mark.parametrize("depth", SUB_DEPTHS)
+def test_bracket_histograms_grouped_sub_cell(ext, sub_cell_column, fine_cols, depth, top):
+    """Brackets 512^depth times narrower than a pass-1 cell, as the second
+    and later refinement passes produce them, at the bottom and at the top
+    of the first, a middle and the last cell: one launch, one bracket per
+    cell. A bracket at the top of a cell ends on the next cell's start (on
+    the end of the grid in the last cell) and must still be found through
+    its own cell's LUT entry, however narrow it is."""
+    cpu, dev = sub_cell_column
+    f32 = next(d for c, d in zip(*fine_cols) if c.dtype == torch.float32 and c.numel() >= 2053)
+    bounds = [_sub_cell_bracket(cell, depth, top) for cell in SUB_CELLS]
+    bc = torch.zeros(len(bounds), dtype=torch.int64)
+    lo = torch.tensor([b[0] for b in bounds], dtype=torch.float64)
+    hi = torch.tensor([b[1] for b in bounds], dtype=torch.float64)
+    p1lo = torch.full((2,), -64.0, dtype=torch.float64)
+    p1scale = torch.full((2,), 16 / 128.0, dtype=torch.float64)
+    # the f32 column carries no bracket and is never read
+    got = ext.bracket_histograms_grouped([dev, f32], bc, lo, hi, p1lo, p1scale, 16).cpu()
+    assert tuple(got.shape) == (len(bounds), 512)
+    for j, (l, h) in enumerate(bounds):
+        want = _bracket_ref(cpu, l, h, 512)
+        assert int(want.min()) >= 1 and int(want.sum()) >= 512  # one planted value per sub-bin
+        assert torch.equal(got[j], want), f"cell {SUB_CELLS[j]}: {int(got[j].sum())} counted, {int(want.sum())} expected"
+
+
 # ----------------------------------------------------------- code counts
 def _codes(n, size, g):
     """int32 codes in [0, size) with nulls and out-of-range values mixed in."""

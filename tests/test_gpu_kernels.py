@@ -279,7 +279,7 @@ def test_outlier_clamp_columns_vs_torch(ext):
 @requires_gpu
 def test_approx_quantiles_sketch_path_vs_torch(ext):
     """Large-n path: pass-1 histogram + LUT-grouped refinement must land
-    within Spark's rel-err 0.01 rank tolerance of torch.quantile."""
+    within Spark's rel-err 0.01 rank tolerance of the sorted data."""
     from anovos_amd.core.frame import AnovosFrame, Column
     from anovos_amd.ops import histogram as hist_ops
 
@@ -298,33 +298,13 @@ def test_approx_quantiles_sketch_path_vs_torch(ext):
     idf = AnovosFrame(cols, device="cuda")
     probs = [0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99]
     got = hist_ops.approx_quantiles(idf, list(specs), probs)
-    for name in specs:
-        x = cols[name].data
-        v = x[~torch.isnan(x)]
-        vs, _ = torch.sort(v)
-        nn = vs.numel()
-        for p, q in zip(probs, got[name]):
-            # rank-tolerance check (Spark approxQuantile contract): the
-            # returned value must sit next to a data value whose rank
-            # interval covers p*n within rel_err (duplicate blocks make a
-            # single-point rank ambiguous)
-            qt = torch.tensor(q, device=vs.device)
-            lo_r = int(torch.searchsorted(vs, qt, right=False))
-            hi_r = int(torch.searchsorted(vs, qt, right=True))
-            # rank intervals of the data values bracketing q
-            cand = [(lo_r, hi_r)]
-            if lo_r > 0:
-                v_below = vs[lo_r - 1]
-                cand.append((int(torch.searchsorted(vs, v_below, right=False)),
-                             int(torch.searchsorted(vs, v_below, right=True))))
-            if hi_r < nn:
-                v_above = vs[hi_r]
-                cand.append((int(torch.searchsorted(vs, v_above, right=False)),
-                             int(torch.searchsorted(vs, v_above, right=True))))
-            tol = max(0.01 * nn, 1000)
-            target = p * nn
-            ok = any(a - tol <= target <= b + tol for a, b in cand)
-            assert ok, (name, p, q, cand, target)
+    # the strict rank contract against a CPU fp64 sort: no allowance for a
+    # neighbouring data value (heavy_dup's 5 % blocks force the data value)
+    from tests.test_quantile_contract import assert_rank_contract
+
+    for name, x in specs.items():
+        vs = torch.sort(x[~torch.isnan(x)].to(torch.float64))[0]
+        assert_rank_contract(vs, probs, got[name], 0.01, name)
 
 
 @requires_gpu
@@ -528,9 +508,7 @@ def test_refinement_many_brackets_and_collisions(ext):
     """>16 refinement brackets per column and brackets
     sharing a pass-1 bin must degrade to extra launches, not crash or
     silently zero. A spiky distribution + 39 quantile probs forces both;
-    results must match the exact sort."""
-    import math
-
+    results must meet the strict rank contract against the sorted data."""
     from anovos_amd.core.frame import AnovosFrame, Column
     from anovos_amd.ops import histogram as hist_ops
 
@@ -543,11 +521,15 @@ def test_refinement_many_brackets_and_collisions(ext):
     idf = AnovosFrame({"x": Column("x", "float", x)}, device="cuda")
     probs = [round(0.025 * j, 4) for j in range(1, 40)]  # 39 probs
     got = hist_ops.approx_quantiles(idf, ["x"], probs)["x"]
-    xs, _ = torch.sort(x)
-    for p, v in zip(probs, got):
-        r = min(max(math.ceil(p * n), 1), n) - 1
-        exact = float(xs[r])
-        assert abs(v - exact) <= max(0.01 * abs(exact), 0.01), (p, v, exact)
+    from tests.test_quantile_contract import assert_rank_contract
+
+    xs = torch.sort(x.cpu().to(torch.float64))[0]
+    assert_rank_contract(xs, probs, got, 0.01, "spiky")
+    # each of the five spikes holds 19 % of the rows, far above the
+    # tolerance, so inside a spike's rank block the contract admits only
+    # the spike itself. In the sorted data 34 of the 39 probabilities lie
+    # more than the tolerance inside a block.
+    assert sum(v in (1.0, 2.0, 3.0, 5.0, 8.0) for v in got) >= 34, got
 
 
 @requires_gpu
