@@ -772,11 +772,13 @@ torch::Tensor centered_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
   auto dptr = to_device_i64(ptrs, device);
   auto gram = torch::zeros({k, k}, torch::TensorOptions().dtype(torch::kFloat32).device(device));
   if (kt <= 13) {
-    // single-read kernel: one block stages a 32-row slab of ALL columns
-    // through LDS; HBM traffic = n*k*4 bytes (vs ~kt x for pair-parallel)
+    // single-read kernel: one block stages 128-row macro-slabs of ALL
+    // columns through LDS; HBM traffic = n*k*4 bytes (vs ~kt x for
+    // pair-parallel)
     const int64_t steps_total = (n + 31) / 32;
-    // one full wave of resident blocks (occupancy x CUs): maximizes each
-    // block's contiguous per-column streams (see anovos_gram_sr_grid)
+    // one full wave of resident blocks (occupancy x CUs), so every block
+    // starts at once and owns one contiguous row range (see
+    // anovos_gram_sr_grid); blocks past the last macro-slab add zeros
     int64_t target_chunks = anovos_gram_sr_grid(k);
     if (const char *e = getenv("ANOVOS_GRAM_CHUNKS")) target_chunks = atoll(e);
     int row_chunks = (int)std::min<int64_t>(target_chunks, std::max<int64_t>(1, steps_total));
