@@ -42,4 +42,6 @@ def fill_nan_columns(tensors: Sequence[torch.Tensor], fills: Sequence[float]) ->
         return ext.fill_nan_columns(
             [t.contiguous() for t in tensors], torch.tensor(list(fills), dtype=torch.float64)
         )
-    return [torch.nan_to_num(t, nan=float(f)) for t, f in zip(tensors, fills)]
+    # NaN only, as the kernel does: nan_to_num would also replace +-inf
+    # (with the dtype's largest finite value)
+    return [torch.where(torch.isnan(t), torch.full_like(t, float(f)), t) for t, f in zip(tensors, fills)]

@@ -155,17 +155,21 @@ def discrete_modes(idf, cols: List[str]) -> Dict[str, Tuple[Optional[float], int
     if dense:
         import numpy as np
 
+        # unit-width bins for EVERY column: M bins over [min, min + M), so
+        # bin idx holds exactly the value min + idx whatever the column's
+        # own range is (bins of width R_i / M < 1 for a narrow column next
+        # to a wide one do not map back to integers); every value lies in
+        # [min, max], so the bins past a column's range stay empty
         R = [int(moments[c].max - moments[c].min) + 1 for c in dense]
         M = max(R)
         tensors = [idf.col(c).data for c in dense]
         lo = torch.tensor([moments[c].min for c in dense], dtype=torch.float64)
-        hi = torch.tensor([moments[c].min + r for c, r in zip(dense, R)], dtype=torch.float64)
+        hi = torch.tensor([moments[c].min + M for c in dense], dtype=torch.float64)
         hist = hist_ops.global_histograms(tensors, lo, hi, M).cpu().numpy()
         for i, c in enumerate(dense):
-            idx = int(np.argmax(hist[i]))
+            idx = int(np.argmax(hist[i][: R[i]]))
             cnt = int(hist[i][idx])
-            val = moments[c].min + int(idx * R[i] / M)
-            out[c] = (float(val), cnt) if cnt > 0 else (None, 0)
+            out[c] = (float(moments[c].min + idx), cnt) if cnt > 0 else (None, 0)
     for c in rest:
         m = moments[c]
         if dist.is_dist() and m.n > 1_000_000 and not m.integral:

@@ -97,7 +97,7 @@ DEV_INLINE void mom_block_reduce_write(MomAcc &a, double *dst) {
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    MomAcc r{0, 0, 0, 0, 0, DBL_MAX, -DBL_MAX, 0, 0};
+    MomAcc r{0, 0, 0, 0, 0, (double)INFINITY, -(double)INFINITY, 0, 0};
     for (int wv = 0; wv < THREADS / 64; ++wv) {
       double *m = &smw[wv * NSTAT];
       r.n += m[0]; r.s1 += m[1]; r.s2 += m[2]; r.s3 += m[3]; r.s4 += m[4];
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(THREADS) void moments_partials_kernel(
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
-  MomAcc a{0, 0, 0, 0, 0, DBL_MAX, -DBL_MAX, 0};
+  MomAcc a{0, 0, 0, 0, 0, (double)INFINITY, -(double)INFINITY, 0};
 
   if (sizeof(T) == 4) {
     // vectorized float4 path: 16 B per lane per iteration
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(THREADS) void moments_partials_kernel(
 __global__ __launch_bounds__(THREADS) void moments_reduce_kernel(
     const double *partials, int nchunks, double *out) {
   const int col = blockIdx.x;
-  MomAcc a{0, 0, 0, 0, 0, DBL_MAX, -DBL_MAX, 0, 0};
+  MomAcc a{0, 0, 0, 0, 0, (double)INFINITY, -(double)INFINITY, 0, 0};
   for (int c = threadIdx.x; c < nchunks; c += THREADS) {
     const double *p = &partials[((int64_t)col * nchunks + c) * NSTAT];
     a.n += p[0]; a.s1 += p[1]; a.s2 += p[2]; a.s3 += p[3]; a.s4 += p[4];
@@ -1542,7 +1542,7 @@ __global__ __launch_bounds__(THREADS) void moments_hll_kernel(
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
-  MomAcc a{0, 0, 0, 0, 0, DBL_MAX, -DBL_MAX, 0};
+  MomAcc a{0, 0, 0, 0, 0, (double)INFINITY, -(double)INFINITY, 0};
   auto body = [&](T v) {
     mom_add(a, (double)v, shift);
     int idx, rho;

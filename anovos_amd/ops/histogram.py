@@ -115,11 +115,12 @@ def _exact_quantiles(idf, cols, probs, moments, rel_err=1e-4):
     return out
 
 
-def _exact_integral_quantiles(idf, cols, probs, moments):
+def _exact_integral_quantiles(idf, cols, probs, moments, rel_err=0.0):
     """Exact quantiles for integer-valued columns via one dense
-    integer-aligned histogram (bin width exactly 1.0): rank = ceil(p*n),
-    value = first integer whose CDF reaches the rank — the same rank
-    convention as the exact sort path (Spark GK returns data elements)."""
+    integer-aligned histogram (bin width exactly 1.0): p <= rel_err ->
+    min, p >= 1 - rel_err -> max, else rank = ceil(p*n); value = first
+    integer whose CDF reaches the rank — the same query rule as the exact
+    sort path (Spark GK returns data elements)."""
     import math as _math
 
     import numpy as np
@@ -146,7 +147,12 @@ def _exact_integral_quantiles(idf, cols, probs, moments):
         cdf = np.cumsum(counts)
         vals = []
         for p in probs:
-            r = min(max(int(_math.ceil(p * n)), 1), n)
+            if p <= rel_err:
+                r = 1
+            elif p >= 1 - rel_err:
+                r = n
+            else:
+                r = min(max(int(_math.ceil(p * n)), 1), n)
             b = int(np.searchsorted(cdf, r, side="left"))
             vals.append(float(cmin + min(b, R[c] - 1)))
         out[c] = vals
@@ -256,7 +262,7 @@ def approx_quantiles(
         and any(("q", p) not in idf.col(c).cache for p in probs_l)
     ]
     if int_cols:
-        dense = _exact_integral_quantiles(idf, int_cols, probs_l, moments)
+        dense = _exact_integral_quantiles(idf, int_cols, probs_l, moments, rel_err=rel_err)
         for c in int_cols:
             for j, p in enumerate(probs_l):
                 idf.col(c).cache[("q", p)] = dense[c][j]

@@ -101,15 +101,20 @@ def merge_moments_global(local: torch.Tensor) -> torch.Tensor:
     if not dist.is_dist():
         return local.cpu()
     sums = local[:, [0, 1, 2, 3, 4, 7, 8]].contiguous()
-    mn = torch.nan_to_num(local[:, 5], nan=float("inf")).contiguous()
-    mx = torch.nan_to_num(local[:, 6], nan=float("-inf")).contiguous()
+    # NaN (a rank without valid rows) must not win the reduction; torch.where,
+    # not nan_to_num, which would also turn infinite extrema into +-DBL_MAX
+    mn = torch.where(torch.isnan(local[:, 5]), torch.full_like(local[:, 5], float("inf")), local[:, 5]).contiguous()
+    mx = torch.where(torch.isnan(local[:, 6]), torch.full_like(local[:, 6], float("-inf")), local[:, 6]).contiguous()
     dist.all_reduce_(sums, "sum")
     dist.all_reduce_(mn, "min")
     dist.all_reduce_(mx, "max")
     out = torch.empty_like(local)
     out[:, [0, 1, 2, 3, 4, 7, 8]] = sums
-    out[:, 5] = torch.where(torch.isinf(mn), torch.full_like(mn, float("nan")), mn)
-    out[:, 6] = torch.where(torch.isinf(mx), torch.full_like(mx, float("nan")), mx)
+    # a column is null on every rank when the summed n is 0 — an infinite
+    # extremum is data (a column that holds -inf keeps its min)
+    empty = sums[:, 0] == 0
+    out[:, 5] = torch.where(empty, torch.full_like(mn, float("nan")), mn)
+    out[:, 6] = torch.where(empty, torch.full_like(mx, float("nan")), mx)
     return out.cpu()
 
 

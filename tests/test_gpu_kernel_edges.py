@@ -155,6 +155,83 @@ def test_column_moments_infinities(ext, dtype):
     assert got[0] == 6 and got[5] == -INF and got[6] == INF and got[7] == 2 and got[8] == 1
 
 
+# Infinities of ONE sign: min / max accumulators that start at +-DBL_MAX
+# never reach +inf / -inf (fmin(DBL_MAX, inf) is DBL_MAX).
+_ONE_SIGN_INF = [[INF, INF, NAN], [-INF], [INF, 1.0], [-INF, 1.0], [INF] * 2053]
+
+
+def _same_or_both_nan(got, want):
+    """Strict: NaN where the reference has NaN, equal elsewhere, where inf
+    equals only inf of the same sign (_eq_nan's nan_to_num would make inf
+    and DBL_MAX compare equal)."""
+    return torch.equal(torch.isnan(got), torch.isnan(want)) and bool(((got == want) | torch.isnan(want)).all())
+
+
+def _check_moments_strict(got, cpu_cols, shifts):
+    got = got.cpu()
+    assert got.dtype == torch.float64 and tuple(got.shape) == (len(cpu_cols), 9)
+    for i, x in enumerate(cpu_cols):
+        want = _moments_ref(x, shifts[i] if shifts else 0.0)
+        assert _same_or_both_nan(got[i], want), f"column {i} (n={x.numel()}, {x.dtype}): {got[i].tolist()} vs {want.tolist()}"
+
+
+def _one_sign_inf_cols(dtype):
+    return [torch.tensor(v, dtype=dtype) for v in _ONE_SIGN_INF]
+
+
+def test_moments_reference_on_one_signed_infinities():
+    """What the fp64 reference says: the extremum is the infinity, the odd
+    power sums carry its sign, nothing is NaN."""
+    ref = [_moments_ref(x, 0.0) for x in _one_sign_inf_cols(torch.float64)]
+    assert [(r[0].item(), r[5].item(), r[6].item()) for r in ref] == [
+        (2, INF, INF), (1, -INF, -INF), (2, 1.0, INF), (2, -INF, 1.0), (2053, INF, INF)]
+    assert ref[3][1:5].tolist() == [-INF, INF, -INF, INF] and ref[2][1:5].tolist() == [INF] * 4
+    assert all(r[7] == 0 and r[8] == 0 for r in ref)
+
+
+@requires_gpu
+@pytest.mark.gpu
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_moments_one_signed_infinities(ext, dtype, shifted):
+    """n, min, max, zeros and n_frac equal the reference; the power sums
+    are +-inf exactly where the reference's are (no NaN arises: only one
+    sign is present). Plain and fused kernel."""
+    cpu = _one_sign_inf_cols(dtype)
+    dev = [_dev(x) for x in cpu]
+    shifts = [0.5, -2.0, 1.0, 0.0, 3.5] if shifted else []
+    _check_moments_strict(ext.column_moments(dev, shifts), cpu, shifts)
+    _check_moments_strict(ext.moments_hll(dev, 12, shifts)[0], cpu, shifts)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_moments_one_signed_infinities_cpu_path(dtype):
+    from anovos_amd.ops import stats
+
+    cpu = _one_sign_inf_cols(dtype)
+    for shifts in ([0.0] * 5, [0.5, -2.0, 1.0, 0.0, 3.5]):
+        _check_moments_strict(stats.column_moments_local(cpu, shifts), cpu, shifts)
+
+
+def test_merge_moments_global_keeps_infinite_extrema(monkeypatch):
+    """A one-rank world (is_dist patched to true, the all-reduce to the
+    identity): the merge returns what it was given. Finite and infinite
+    extrema survive; only the row with n = 0 has NaN min / max."""
+    from anovos_amd.core import dist
+    from anovos_amd.ops import stats
+
+    monkeypatch.setattr(dist, "is_dist", lambda: True)
+    monkeypatch.setattr(dist, "all_reduce_", lambda t, op="sum": t)
+    cols = [torch.tensor(v, dtype=torch.float64) for v in
+            ([-INF, 1.0, 2.0], [INF, 1.0], [NAN, NAN], [-1.5, 4.0, 0.0], [INF, NAN], [-INF])]
+    local = torch.stack([_moments_ref(x, 0.0) for x in cols])
+    assert local[:, 5].tolist()[:2] == [-INF, 1.0] and local[:, 6].tolist()[:2] == [2.0, INF]
+    got = stats.merge_moments_global(local.clone())
+    assert _same_or_both_nan(got, local), (got.tolist(), local.tolist())
+    assert torch.isnan(got[:, 5:7]).any(dim=1).tolist() == [False, False, True, False, False, False]
+    assert got[2, 0] == 0
+
+
 # ------------------------------------------------------------------- HLL
 _M32 = (1 << 32) - 1
 _M64 = (1 << 64) - 1
