@@ -392,3 +392,152 @@ def IG_calculation(
     if print_impact:
         print(odf.to_string(index=False))
     return odf
+
+
+def _association_stats(tab: np.ndarray, bias_correction: bool = False):
+    """(cramers_v, mutual_info, u_row_given_col, u_col_given_row) of one
+    contingency table whose LAST row and column are the null slots — fp64
+    numpy throughout. The null row/column go first (pairwise-complete
+    rows), then categories without a row left; N, r, c are what remains.
+    mutual_info is in nats; u_row_given_col = MI / H(row variable).
+    Undefined entries are NaN."""
+    nan = float("nan")
+    t = np.asarray(tab, dtype=np.float64)[:-1, :-1]
+    t = t[t.sum(axis=1) > 0][:, t.sum(axis=0) > 0] if t.size else t
+    n = float(t.sum()) if t.size else 0.0
+    if n <= 0:
+        return nan, nan, nan, nan
+    r, c = t.shape
+    ri = t.sum(axis=1)
+    cj = t.sum(axis=0)
+    expected = np.outer(ri, cj) / n
+    phi2 = float((((t - expected) ** 2) / expected).sum()) / n
+    v = nan
+    if min(r, c) >= 2:
+        if not bias_correction:
+            v = math.sqrt(phi2 / min(r - 1, c - 1))
+        elif n >= 2:
+            # Bergsma (2013)
+            phi2c = max(0.0, phi2 - (r - 1) * (c - 1) / (n - 1))
+            rt = r - (r - 1) ** 2 / (n - 1)
+            ct = c - (c - 1) ** 2 / (n - 1)
+            den = min(rt - 1, ct - 1)
+            if den > 0:
+                v = math.sqrt(phi2c / den)
+    nz = t > 0
+    mi = max(0.0, float((t[nz] / n * np.log(t[nz] * n / np.outer(ri, cj)[nz])).sum()))
+    h_row = -float((ri / n * np.log(ri / n)).sum())
+    h_col = -float((cj / n * np.log(cj / n)).sum())
+    u_row = mi / h_row if h_row > 0 else nan
+    u_col = mi / h_col if h_col > 0 else nan
+    return v, mi, u_row, u_col
+
+
+@traced
+def categorical_association_matrix(
+    ctx,
+    idf,
+    list_of_cols="all",
+    drop_cols=[],
+    method_type="cramers_v",
+    bias_correction=False,
+    encoding_configs={"bin_method": "equal_frequency", "bin_size": 10},
+    max_categories=1000,
+    print_impact=False,
+):
+    """[attribute, <cols...>] — association between categorical attributes
+    (numerical ones are binned first), beyond the reference, which only
+    offers Pearson over label-encoded codes for this.
+
+    method_type: "cramers_v" (symmetric, [0, 1]; bias_correction=True
+    applies Bergsma's correction), "mutual_info" (symmetric, nats) or
+    "theils_u" (entry [row x, column y] = MI(x, y) / H(x), asymmetric).
+    Every pair uses its pairwise-complete rows; undefined entries (no
+    complete row, a constant column where the measure needs two
+    categories) are NaN. Categorical columns with more than
+    max_categories dictionary entries are left out with a warning. One
+    pass of the pair-count kernel (K22) yields all contingency tables;
+    the statistics are fp64 numpy on the host, not rounded."""
+    from anovos_amd.core.frame import AnovosFrame, Column
+    from anovos_amd.ops.contingency import pair_contingency_tables
+    from anovos_amd.ops.groupby import align_dictionaries
+
+    if method_type not in ("cramers_v", "mutual_info", "theils_u"):
+        raise TypeError("Invalid input for method_type")
+    num_cols, cat_cols, _ = attributeType_segregation(idf)
+    if list_of_cols == "all":
+        list_of_cols = num_cols + cat_cols
+    if isinstance(list_of_cols, str):
+        list_of_cols = [x.strip() for x in list_of_cols.split("|")]
+    if isinstance(drop_cols, str):
+        drop_cols = [x.strip() for x in drop_cols.split("|")]
+    cols = [e for e in dict.fromkeys(list_of_cols) if e not in list(drop_cols)]
+    if any(x not in num_cols + cat_cols for x in cols) or len(cols) == 0:
+        raise TypeError("Invalid input for Column(s)")
+
+    my_cat = [c for c in cols if c in cat_cols]
+    my_num = [c for c in cols if c in num_cols]
+    # dictionary sizes decide which columns stay: make them rank-identical first
+    align_dictionaries(idf, my_cat)
+    too_wide = [c for c in my_cat if len(idf.col(c).dictionary or []) > max_categories]
+    if too_wide:
+        warnings.warn(
+            "categorical_association_matrix: more than " + str(max_categories)
+            + " categories, column(s) left out: " + ", ".join(too_wide)
+        )
+        cols = [c for c in cols if c not in too_wide]
+    if len(cols) == 0:
+        raise TypeError("Invalid input for Column(s)")
+
+    work = {c: idf.col(c) for c in cols if c in cat_cols}
+    if my_num:
+        bin_size = int(encoding_configs["bin_size"])
+        binned = attribute_binning(
+            ctx, idf.select(my_num), my_num, [], encoding_configs["bin_method"], bin_size,
+            "numerical", False, "NA", "append",
+        )
+        labels = [str(b) for b in range(1, bin_size + 1)]
+        for c in my_num:
+            if c + "_binned" in binned:
+                b = binned.col(c + "_binned").data  # bin label 1..bin_size, NaN = null
+                codes = torch.where(torch.isnan(b), torch.full_like(b, NULL_CODE), b - 1).to(torch.int32)
+            else:  # all-null column: binning warned and left it out
+                codes = torch.full((idf.local_rows(),), NULL_CODE, dtype=torch.int32, device=idf.device)
+            work[c] = Column(c, "string", codes, labels)
+            work[c].cache["dict_aligned"] = True  # same labels on every rank
+    wf = AnovosFrame({c: work[c] for c in cols}, idf.device)
+
+    k = len(cols)
+    pairs = [(cols[a], cols[b]) for a in range(k) for b in range(a + 1, k)]
+    if k == 1:
+        pairs = [(cols[0], cols[0])]  # only the marginal is needed
+    tables = pair_contingency_tables(wf, cols, pairs)
+
+    pick = {"cramers_v": 0, "mutual_info": 1, "theils_u": 2}[method_type]
+    mat = np.full((k, k), np.nan, dtype=np.float64)
+    for a in range(k):
+        # diagonal: the column against itself is the diagonal table of its
+        # marginal (rows of any of its tables, null column included)
+        if k == 1:
+            marg = np.diag(tables[pairs[0]])
+        elif a + 1 < k:
+            marg = tables[(cols[a], cols[a + 1])].sum(axis=1)
+        else:
+            marg = tables[(cols[a - 1], cols[a])].sum(axis=0)
+        m = marg[:-1]
+        diag = np.zeros((m.size + 1, m.size + 1), dtype=np.int64)
+        diag[np.arange(m.size), np.arange(m.size)] = m
+        st = _association_stats(diag, bias_correction)
+        # a constant (or empty) column has no association with itself
+        mat[a, a] = st[pick] if np.count_nonzero(m) >= 2 else np.nan
+        for b in range(a + 1, k):
+            st = _association_stats(tables[(cols[a], cols[b])], bias_correction)
+            mat[a, b] = st[pick]
+            mat[b, a] = st[3] if method_type == "theils_u" else st[pick]
+    odf = pd.DataFrame(mat, columns=cols, index=cols)
+    odf["attribute"] = odf.index
+    sorted_cols = sorted(cols)
+    odf = odf[["attribute"] + sorted_cols].sort_values("attribute").reset_index(drop=True)
+    if print_impact:
+        print(odf.to_string(index=False))
+    return odf

@@ -95,6 +95,9 @@ int anovos_label_counts_multi(const void *const *cols, const uint8_t *label,
                               const int *sizes, const int *dtypes, int ncols,
                               int max_slots, int nchunks, uint64_t *out,
                               hipStream_t stream);
+int anovos_pair_code_counts(const int32_t *const *cols, const int64_t *items,
+                            int nitems, int64_t n, int64_t per, int nchunks,
+                            int lds_slots, uint64_t *out, hipStream_t stream);
 }
 
 namespace {
@@ -850,6 +853,140 @@ torch::Tensor code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int
   return out;
 }
 
+// K22: contingency tables of column pairs. The kernel (pair_counts.hip)
+// takes work items "anchor column + up to kPairPmax partners"; the three
+// constants mirror PAIR_PMAX / PAIR_LDS_SLOTS / PAIR_ITEM_WORDS there.
+namespace {
+
+constexpr int kPairPmax = 8;
+constexpr int64_t kPairLdsSlots = 16384;
+constexpr int kPairItemWords = 4 + 4 * kPairPmax;
+
+struct PairPlan {
+  std::vector<int64_t> items;  // kPairItemWords words per item
+  std::vector<int64_t> offs;   // output offset of every pair's table
+  int64_t total = 0;           // cells of all tables
+  int nitems = 0;
+  int lds_slots = 0;           // most counters any STAGED item needs
+  int64_t col_reads = 0;       // column streams per row chunk: sum(1 + partners)
+};
+
+// Pairs are grouped by their first column (the anchor, in order of first
+// appearance) and packed greedily in pair order: an item closes when it
+// has kPairPmax partners or the next table would not fit the LDS budget.
+// A table with more cells than the budget is an item of its own that
+// counts in global memory, so it never sizes the launch's LDS.
+PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<int64_t> &pair_i,
+                         const std::vector<int64_t> &pair_j) {
+  const int64_t ncols = (int64_t)sizes.size();
+  TORCH_CHECK(pair_i.size() == pair_j.size(), "pair_i/pair_j length mismatch");
+  for (auto s : sizes) TORCH_CHECK(s >= 0 && s < INT32_MAX, "dictionary size out of range");
+  PairPlan plan;
+  std::vector<std::vector<int64_t>> by_anchor(ncols);
+  std::vector<int64_t> order;
+  for (size_t q = 0; q < pair_i.size(); ++q) {
+    TORCH_CHECK(pair_i[q] >= 0 && pair_i[q] < ncols && pair_j[q] >= 0 && pair_j[q] < ncols,
+                "pair index out of range");
+    if (by_anchor[pair_i[q]].empty()) order.push_back(pair_i[q]);
+    by_anchor[pair_i[q]].push_back((int64_t)q);
+    plan.offs.push_back(plan.total);
+    plan.total += (sizes[pair_i[q]] + 1) * (sizes[pair_j[q]] + 1);
+  }
+  auto open_item = [&](int64_t a) {
+    plan.items.resize(plan.items.size() + kPairItemWords, 0);
+    int64_t *it = plan.items.data() + (int64_t)plan.nitems * kPairItemWords;
+    it[0] = a;
+    it[1] = sizes[a];
+    plan.nitems += 1;
+    plan.col_reads += 1;
+  };
+  auto add_partner = [&](int64_t q, int64_t lds_off) {
+    int64_t *it = plan.items.data() + (int64_t)(plan.nitems - 1) * kPairItemWords;
+    int64_t *pp = it + 4 + 4 * it[2];
+    pp[0] = pair_j[q];
+    pp[1] = sizes[pair_j[q]];
+    pp[2] = lds_off;
+    pp[3] = plan.offs[q];
+    it[2] += 1;
+    plan.col_reads += 1;
+  };
+  for (int64_t a : order) {
+    int64_t used = 0;
+    int nparts = 0;
+    bool open = false;
+    for (int64_t q : by_anchor[a]) {
+      const int64_t cells = (sizes[a] + 1) * (sizes[pair_j[q]] + 1);
+      if (cells > kPairLdsSlots) {
+        // word 3 stays 0: global-atomic item; the items are appended in
+        // order, so it also closes the staged item that was open
+        open_item(a);
+        add_partner(q, 0);
+        open = false;
+        continue;
+      }
+      if (!open || nparts == kPairPmax || used + cells > kPairLdsSlots) {
+        open_item(a);
+        open = true;
+        used = 0;
+        nparts = 0;
+      }
+      add_partner(q, used);
+      used += cells;
+      nparts += 1;
+      plan.items[(int64_t)(plan.nitems - 1) * kPairItemWords + 3] = used;
+      plan.lds_slots = std::max(plan.lds_slots, (int)used);
+    }
+  }
+  return plan;
+}
+
+}  // namespace
+
+// Flat int64 of the row-major tables [sizes[i]+1][sizes[j]+1] of the pairs
+// (pair_i[p], pair_j[p]), in pair order; the null slot (any code outside
+// [0, size)) is each table's last row / last column.
+torch::Tensor pair_code_counts(std::vector<torch::Tensor> cols, std::vector<int64_t> sizes,
+                               std::vector<int64_t> pair_i, std::vector<int64_t> pair_j) {
+  TORCH_CHECK(!cols.empty(), "no columns");
+  TORCH_CHECK(cols.size() == sizes.size(), "sizes mismatch");
+  auto device = cols[0].device();
+  TORCH_CHECK(device.is_cuda(), "pair_code_counts: device columns required");
+  check_cols(cols, device, "pair_code_counts");
+  const int64_t n = cols[0].numel();
+  std::vector<int64_t> ptrs;
+  for (auto &t : cols) {
+    TORCH_CHECK(t.scalar_type() == torch::kInt32, "int32 code columns required");
+    TORCH_CHECK(t.dim() == 1 && t.numel() == n, "columns must be 1-D and of equal length");
+    ptrs.push_back((int64_t)t.data_ptr());
+  }
+  PairPlan plan = plan_pair_items(sizes, pair_i, pair_j);
+  auto out = torch::zeros({plan.total}, torch::TensorOptions().dtype(torch::kInt64).device(device));
+  if (n == 0 || plan.nitems == 0) return out;
+  int nchunks = pick_chunks(n, plan.nitems);
+  // chunk length a multiple of 4 rows: every chunk then starts at the same
+  // offset inside a 16-byte line as the column itself
+  const int64_t per = (((n + nchunks - 1) / nchunks) + 3) / 4 * 4;
+  // a staged counter holds at most one block's rows
+  TORCH_CHECK(per <= (int64_t)UINT32_MAX, "rows per block exceed the 32-bit LDS counters");
+  TORCH_CHECK((int64_t)plan.nitems * nchunks <= (int64_t)INT32_MAX, "grid too large");
+  auto dptr = to_device_i64(ptrs, device);
+  auto ditems = to_device_i64(plan.items, device);
+  check_hip(anovos_pair_code_counts((const int32_t *const *)dptr.data_ptr<int64_t>(),
+                                    ditems.data_ptr<int64_t>(), plan.nitems, n, per, nchunks,
+                                    plan.lds_slots, (uint64_t *)out.data_ptr<int64_t>(),
+                                    current_stream()),
+            "anovos_pair_code_counts");
+  return out;
+}
+
+// [work items, column streams per row chunk, LDS counters of the launch]
+// for a pair list — what the benchmark needs to count the bytes read.
+std::vector<int64_t> pair_code_counts_plan(std::vector<int64_t> sizes, std::vector<int64_t> pair_i,
+                                           std::vector<int64_t> pair_j) {
+  PairPlan plan = plan_pair_items(sizes, pair_i, pair_j);
+  return {(int64_t)plan.nitems, plan.col_reads, (int64_t)plan.lds_slots};
+}
+
 // K9 fused: label-conditioned histograms, ALL columns in one launch.
 // Per column at out[off]: [slots] totals then [slots] event counts.
 // Column dtype drives the slot mapping (f32 binned vs int32 codes).
@@ -1075,6 +1212,9 @@ std::tuple<torch::Tensor, torch::Tensor> moments_hll(std::vector<torch::Tensor> 
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("code_counts_multi", &code_counts_multi, "fused multi-column code counts + null slot (K5)");
+  m.def("pair_code_counts", &pair_code_counts, "contingency tables of code-column pairs (K22)");
+  m.def("pair_code_counts_plan", &pair_code_counts_plan,
+        "[items, column streams, LDS counters] of a K22 pair list");
   m.def("outlier_clamp_columns", &outlier_clamp_columns, "fused outlier count/clamp (K10/K11)");
   m.def("label_counts_multi", &label_counts_multi, "fused multi-column label-conditioned histograms (K9)");
   m.def("bucketize_label_counts", &bucketize_label_counts, "fused bucketize + label counts, no binned materialization (K6+K9)");

@@ -26,6 +26,7 @@ def build(verbose: bool = True) -> str:
             os.path.join(HERE, "anovos_bindings.hip"),
             os.path.join(HERE, "anovos_kernels.hip"),
             os.path.join(HERE, "corr_mfma.hip"),
+            os.path.join(HERE, "pair_counts.hip"),
         ],
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],

@@ -1,0 +1,124 @@
+"""categorical_association_matrix over two gloo ranks equals the
+single-process result: integer tables merge with one all-reduce, so
+tables and matrices are compared exactly.
+
+Case "disjoint": column `g` has rank-disjoint categories, so its
+per-rank dictionaries differ in size and order until
+align_dictionaries heals them. Case "empty": rank 1 holds no rows and
+must still take part in every collective."""
+
+import json
+import multiprocessing as mp
+import os
+import socket
+
+import numpy as np
+import pandas as pd
+import pytest
+
+
+@pytest.fixture(autouse=True)
+def _gloo_backend(monkeypatch):
+    """The spawned workers inherit this; without it a machine with one
+    visible GPU picks RCCL and refuses two ranks on the same device."""
+    monkeypatch.setenv("ANOVOS_AMD_DIST_BACKEND", "gloo")
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+N = 1200
+CATS = ["g", "h", "w"]
+
+
+def _make_pdf():
+    rng = np.random.default_rng(99)
+    half = N // 2
+    # first half (rank 0): g in {a, b, c}; second half (rank 1): g in {x, y}
+    g = np.concatenate([rng.choice(["a", "b", "c"], half), rng.choice(["x", "y"], N - half)]).astype(object)
+    h = np.where(rng.random(N) < 0.6, np.char.add(g.astype(str), "_h"), rng.choice(["p", "q"], N)).astype(object)
+    w = rng.choice(["u", "v", "w"], N).astype(object)
+    w[rng.choice(N, 40, replace=False)] = None
+    z = rng.integers(0, 4, N).astype(np.float64) + (g == "a")
+    return pd.DataFrame({"g": g, "h": h, "w": w, "z": z})
+
+
+def _shard(pdf, case, rank):
+    if case == "disjoint":
+        half = len(pdf) // 2
+        return pdf.iloc[rank * half : (rank + 1) * half]
+    return pdf if rank == 0 else pdf.iloc[0:0]  # "empty": rank 1 holds nothing
+
+
+def _compute(ctx, idf):
+    from anovos_amd.data_analyzer import association_evaluator as ae
+    from anovos_amd.ops.contingency import pair_contingency_tables
+
+    tables = pair_contingency_tables(idf, CATS)
+    res = {"tables": {a + "|" + b: t.tolist() for (a, b), t in tables.items()},
+           "dicts": {c: list(idf.col(c).dictionary) for c in CATS}}
+    for method in ("cramers_v", "mutual_info", "theils_u"):
+        m = ae.categorical_association_matrix(ctx, idf, method_type=method)
+        res[method] = {"columns": list(m.columns), "attribute": list(m["attribute"]),
+                       "values": m[list(m["attribute"])].to_numpy(dtype=np.float64).tolist()}
+    return res
+
+
+def _worker(rank, port, case, out_path):
+    os.environ.update({"RANK": str(rank), "LOCAL_RANK": str(rank), "WORLD_SIZE": "2",
+                       "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port)})
+    import torch.distributed as td
+
+    from anovos_amd.core import dist
+    from anovos_amd.core.frame import AnovosFrame
+    from anovos_amd.shared.context import init_context
+
+    dist.init_from_env(timeout_s=120)
+    ctx = init_context("cpu")
+    shard = _shard(_make_pdf(), case, rank).reset_index(drop=True)
+    idf = AnovosFrame.from_pandas(shard, device="cpu")
+    res = _compute(ctx, idf)
+    if rank == 0:
+        with open(out_path, "w") as f:
+            json.dump(res, f)
+    td.barrier()
+    td.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def single():
+    """The single-process result, computed once for both cases."""
+    from anovos_amd.core.frame import AnovosFrame
+    from anovos_amd.shared.context import AnovosContext
+
+    return json.loads(json.dumps(_compute(AnovosContext("cpu"), AnovosFrame.from_pandas(_make_pdf(), device="cpu"))))
+
+
+@pytest.mark.parametrize("case", ["disjoint", "empty"])
+def test_two_ranks_match_single_process(tmp_path, single, case):
+    port = _free_port()
+    out = str(tmp_path / "res.json")
+    mp_ctx = mp.get_context("spawn")
+    procs = [mp_ctx.Process(target=_worker, args=(r, port, case, out)) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=180)
+        assert p.exitcode == 0, f"worker failed: exit {p.exitcode}"
+    with open(out) as f:
+        res = json.load(f)
+    assert res["dicts"] == single["dicts"]
+    assert res["dicts"]["g"] == ["a", "b", "c", "x", "y"]
+    assert res["tables"] == single["tables"]
+    total = sum(sum(row) for row in res["tables"]["g|h"])
+    assert total == N
+    for method in ("cramers_v", "mutual_info", "theils_u"):
+        assert res[method]["columns"] == single[method]["columns"]
+        assert res[method]["attribute"] == single[method]["attribute"]
+        np.testing.assert_array_equal(np.array(res[method]["values"], dtype=np.float64),
+                                      np.array(single[method]["values"], dtype=np.float64))
