@@ -1,104 +1,24 @@
-// Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip).
-// Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
-// from the caller's current torch HIP stream so kernels compose with the
-// engine's side-stream overlap (core/dist.py SideStream).
+// Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
+// corr_mfma.hip, pair_counts.hip). Compiled by torch.utils.cpp_extension
+// with hipcc for gfx950; streams come from the caller's current torch HIP
+// stream so kernels compose with the engine's side-stream overlap
+// (core/dist.py SideStream).
+//
+// Every binding has the same shape: gather_columns() validates the column
+// list, the binding validates its other arguments, and only then is
+// anything allocated, uploaded or launched. Mixed f32 / f64 lists run one
+// launch per dtype (split_by_dtype) and scatter back by original position.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-#include <vector>
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
-extern "C" {
-int anovos_moments(const void *const *cols, const int64_t *lens,
-                   const double *shifts, int ncols, int nchunks, int dtype,
-                   double *partials, double *out, hipStream_t stream);
-int anovos_hist(const void *const *cols, const int64_t *lens, int ncols,
-                const double *lo, const double *hi, int nbins, int nchunks,
-                int dtype, uint64_t *out, hipStream_t stream);
-int anovos_bracket_hist(const void *const *cols, const int64_t *lens,
-                        const int64_t *colidx, int nbrackets, const double *lo,
-                        const double *hi, int nbins, int nchunks, int dtype,
-                        uint64_t *out, hipStream_t stream);
-int anovos_bucketize(const void *const *cols, const int64_t *lens, int ncols,
-                     const double *cutflat, const int64_t *cutoff_off,
-                     const int *cutoff_len, int max_ncut, int nchunks, int dtype,
-                     int32_t *const *outs, hipStream_t stream);
-int anovos_code_counts(const int32_t *codes, int64_t n, int size, int nchunks,
-                       uint64_t *out, hipStream_t stream);
-int anovos_hll(const void *x, int64_t n, int p, int nchunks, int dtype,
-               int32_t *regs, hipStream_t stream);
-int anovos_row_null(const void *const *cols, int ncols, int64_t n, int dtype,
-                    int32_t *out, hipStream_t stream);
-int anovos_hll_multi(const void *const *cols, const int64_t *lens, int ncols,
-                     int p, int nchunks, int dtype, int32_t *regs,
-                     hipStream_t stream);
-int anovos_axpb(const void *const *cols, const int64_t *lens, int ncols,
-                const double *a, const double *b, int nchunks, int dtype,
-                float *const *outs, hipStream_t stream);
-int anovos_fillnan(const void *const *cols, const int64_t *lens, int ncols,
-                   const double *fill, int nchunks, int dtype,
-                   void *const *outs, hipStream_t stream);
-int anovos_bracket_hist_grouped(const void *const *cols, const int64_t *lens,
-                                const int *bstart, int ncols, const double *lo,
-                                const double *hi, const double *p1lo,
-                                const double *p1scale, int p1bins, int nchunks,
-                                int dtype, uint64_t *out, hipStream_t stream);
-int anovos_bucketize_float(const void *const *cols, const int64_t *lens, int ncols,
-                           const double *cutflat, const int64_t *cutoff_off,
-                           const int *cutoff_len, int max_ncut, int nchunks, int dtype,
-                           float *const *outs, hipStream_t stream);
-int anovos_bucketize_float_counts(const void *const *cols, const int64_t *lens, int ncols,
-                                  const double *cutflat, const int64_t *cutoff_off,
-                                  const int *cutoff_len, int max_ncut, int nchunks, int dtype,
-                                  float *const *outs, uint64_t *counts, const int64_t *count_off,
-                                  hipStream_t stream);
-int anovos_lut_apply_f32(const int32_t *const *cols, const int64_t *lens, int ncols,
-                         const float *lutflat, const int64_t *lut_off, int nchunks,
-                         float *const *outs, hipStream_t stream);
-int anovos_lut_apply_i32(const int32_t *const *cols, const int64_t *lens, int ncols,
-                         const int32_t *lutflat, const int64_t *lut_off, int nchunks,
-                         int32_t *const *outs, hipStream_t stream);
-int anovos_fill_code(const int32_t *const *cols, const int64_t *lens, int ncols,
-                     const int32_t *fill, int nchunks, int32_t *const *outs,
-                     hipStream_t stream);
-int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
-                             const int64_t *offs, const int *sizes, int ncols,
-                             int lds_slots, int nchunks, uint64_t *out,
-                             hipStream_t stream);
-int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
-                         int ncols, const double *lo, const double *hi,
-                         int nchunks, int mode, int dtype, void *const *outs,
-                         uint64_t *counts, hipStream_t stream);
-int anovos_moments_hll(const void *const *cols, const int64_t *lens,
-                       const double *shifts, int ncols, int p, int nchunks,
-                       int dtype, double *partials, double *mom_out,
-                       int32_t *regs, hipStream_t stream);
-int anovos_centered_gram(const void *const *cols, int64_t n, int k,
-                         const float *means, const int *pair_i,
-                         const int *pair_j, int npairs, int row_chunks,
-                         float *partials, float *gram, hipStream_t stream);
-int anovos_centered_gram_sr(const void *const *cols, int64_t n, int k,
-                            const float *means, const int *pair_i,
-                            const int *pair_j, int npairs, int row_chunks,
-                            float *partials, float *gram, hipStream_t stream);
-int anovos_gram_sr_grid(int k);
-int anovos_bucketize_label_counts(const void *const *cols, const uint8_t *label,
-                                  const int64_t *lens, const double *cutflat,
-                                  const int64_t *cutoff_off, const int *cutoff_len,
-                                  const int64_t *offs, const int *sizes, int ncols,
-                                  int max_ncut, int max_slots, int nchunks,
-                                  int dtype, uint64_t *out, hipStream_t stream);
-int anovos_label_counts_multi(const void *const *cols, const uint8_t *label,
-                              const int64_t *lens, const int64_t *offs,
-                              const int *sizes, const int *dtypes, int ncols,
-                              int max_slots, int nchunks, uint64_t *out,
-                              hipStream_t stream);
-int anovos_pair_code_counts(const int32_t *const *cols, const int64_t *items,
-                            int nitems, int64_t n, int64_t per, int nchunks,
-                            int lds_slots, uint64_t *out, hipStream_t stream);
-}
+#include "anovos_kernels.h"
 
 namespace {
 
@@ -117,146 +37,336 @@ int pick_chunks(int64_t n, int ncols) {
   return (int)std::max<int64_t>(c, std::max<int64_t>(floor_c, 1));
 }
 
-struct PtrPack {
-  torch::Tensor dev;  // int64 tensor of device pointers
+torch::TensorOptions on(const torch::Device &dev, torch::ScalarType t) {
+  return torch::TensorOptions().dtype(t).device(dev);
+}
+
+// Host array (int64 / int32 / double / float) -> device tensor: a
+// non-blocking copy from a pageable tensor that owns its bytes. An empty
+// array uploads as one zero, so data_ptr() is never null.
+template <typename T>
+torch::Tensor upload(const std::vector<T> &vals, const torch::Device &dev) {
+  auto cpu = torch::zeros({(int64_t)std::max<size_t>(vals.size(), 1)},
+                          torch::TensorOptions().dtype(c10::CppTypeToScalarType<T>::value));
+  if (!vals.empty()) std::memcpy(cpu.template data_ptr<T>(), vals.data(), vals.size() * sizeof(T));
+  return cpu.to(dev, /*non_blocking=*/true);
+}
+
+// An uploaded array of addresses, as the pointer table a launcher takes.
+template <typename T>
+T *const *ptr_table(const torch::Tensor &t) {
+  return (T *const *)t.data_ptr<int64_t>();
+}
+
+template <typename T>
+std::vector<T> pick(const std::vector<T> &vals, const std::vector<int64_t> &idx) {
+  std::vector<T> out;
+  for (int64_t i : idx) out.push_back(vals[i]);
+  return out;
+}
+
+// Allowed column dtypes of a binding: bit (1 << dtype code), where the
+// code is what the launchers take as `dtype`.
+constexpr int F32 = 1, F64 = 2, I32 = 4;
+
+// The columns of one binding call (or, after split_by_dtype, of one
+// launch): every kernel reads a column as a dense array from data_ptr().
+struct ColumnBatch {
+  const char *name;
+  torch::Device device;
+  int dtype = -1;                  // common dtype code, -1 when mixed
+  std::vector<int64_t> ptrs, lens;
+  std::vector<int64_t> idx;        // position in the binding's column list
+  std::vector<int> dtypes;         // 0 f32, 1 f64, 2 int32
+  int64_t maxn = 0;
+
+  int ncols() const { return (int)ptrs.size(); }
+  void add(int64_t ptr, int64_t len, int64_t i, int d) {
+    dtype = ptrs.empty() || dtype == d ? d : -1;
+    ptrs.push_back(ptr);
+    lens.push_back(len);
+    idx.push_back(i);
+    dtypes.push_back(d);
+    maxn = std::max(maxn, len);
+  }
 };
 
-// Upload an array of device pointers / lengths to the GPU.
-torch::Tensor to_device_i64(const std::vector<int64_t> &vals, const torch::Device &dev) {
-  auto cpu = torch::from_blob((void *)vals.data(), {(int64_t)vals.size()},
-                              torch::TensorOptions().dtype(torch::kInt64))
-                 .clone();
-  return cpu.to(dev, /*non_blocking=*/true);
+// Refuses, before anything touches the device: an empty list, host
+// tensors, a second device, strided views, dtypes outside `allowed` and,
+// with equal_len, columns of differing length.
+ColumnBatch gather_columns(const std::vector<torch::Tensor> &cols, const char *name, int allowed,
+                           bool equal_len = false) {
+  TORCH_CHECK(!cols.empty(), name, ": no columns");
+  ColumnBatch b{name, cols[0].device()};
+  TORCH_CHECK(b.device.is_cuda(), name, ": device columns required");
+  for (size_t i = 0; i < cols.size(); ++i) {
+    auto &t = cols[i];
+    TORCH_CHECK(t.device() == b.device, name, ": columns must be on the same device");
+    TORCH_CHECK(t.is_contiguous(), name, ": columns must be contiguous");
+    auto st = t.scalar_type();
+    int d = st == torch::kFloat32 ? 0 : st == torch::kFloat64 ? 1 : st == torch::kInt32 ? 2 : 3;
+    TORCH_CHECK((allowed >> d) & 1, name, ": expected ",
+                allowed == I32 ? "int32 code" : allowed == F32 ? "float32"
+                : allowed == (F32 | F64) ? "float32/float64"
+                : allowed == (F32 | I32) ? "float32/int32" : "float32/float64/int32",
+                " columns, got ", st);
+    TORCH_CHECK(!equal_len || t.numel() == cols[0].numel(), name,
+                ": all columns must have equal length");
+    b.add((int64_t)t.data_ptr(), t.numel(), (int64_t)i, d);
+  }
+  return b;
 }
 
-torch::Tensor to_device_f64(const std::vector<double> &vals, const torch::Device &dev) {
-  auto cpu = torch::from_blob((void *)vals.data(), {(int64_t)vals.size()},
-                              torch::TensorOptions().dtype(torch::kFloat64))
-                 .clone();
-  return cpu.to(dev, /*non_blocking=*/true);
+// The f32 columns, then the f64 columns (then int32): one launch each,
+// empty groups left out. idx keeps the original positions.
+std::vector<ColumnBatch> split_by_dtype(const ColumnBatch &all) {
+  std::vector<ColumnBatch> out;
+  for (int d = 0; d < 3; ++d) {
+    ColumnBatch b{all.name, all.device};
+    for (int j = 0; j < all.ncols(); ++j)
+      if (all.dtypes[j] == d) b.add(all.ptrs[j], all.lens[j], all.idx[j], d);
+    if (b.ncols()) out.push_back(std::move(b));
+  }
+  return out;
 }
 
-int dtype_code(const torch::Tensor &t) {
-  if (t.scalar_type() == torch::kFloat32) return 0;
-  if (t.scalar_type() == torch::kFloat64) return 1;
-  TORCH_CHECK(false, "expected float32/float64 column, got ", t.scalar_type());
-  return -1;
+std::vector<int64_t> out_ptrs(const std::vector<torch::Tensor> &outs, const ColumnBatch &b) {
+  std::vector<int64_t> p;
+  for (int64_t i : b.idx) p.push_back((int64_t)outs[i].data_ptr());
+  return p;
 }
 
-// Every kernel reads a column as a dense array from data_ptr(): a strided
-// view would be read as if dense, a tensor on another device not at all.
-void check_cols(const std::vector<torch::Tensor> &cols, const torch::Device &device,
-                const char *what) {
-  for (auto &t : cols)
-    TORCH_CHECK(t.is_contiguous() && t.device() == device, what,
-                ": columns must be contiguous, same device");
+void check_count(size_t got, size_t want, const char *name, const char *what) {
+  TORCH_CHECK(got == want, name, ": ", what, " has ", got, " entries, expected ", want);
+}
+
+// A per-column / per-bracket parameter array as fp64, on the host ...
+std::vector<double> host_f64(const torch::Tensor &t, size_t count, const char *name,
+                             const char *what) {
+  check_count((size_t)t.numel(), count, name, what);
+  auto c = t.to(torch::kFloat64).cpu().contiguous();
+  return std::vector<double>(c.data_ptr<double>(), c.data_ptr<double>() + c.numel());
+}
+
+// ... or dense on the device.
+torch::Tensor device_f64(const torch::Tensor &t, size_t count, const ColumnBatch &b,
+                         const char *what) {
+  check_count((size_t)t.numel(), count, b.name, what);
+  return t.to(torch::kFloat64).to(b.device).contiguous();
+}
+
+// `label` / `out`: read or written through data_ptr() next to the columns.
+void check_dense_on_device(const torch::Tensor &t, const ColumnBatch &b, const char *what,
+                           torch::ScalarType st, int64_t numel) {
+  TORCH_CHECK(t.device() == b.device && t.is_contiguous() && t.scalar_type() == st, b.name, ": ",
+              what, " must be a contiguous ", st, " tensor on the columns' device");
+  TORCH_CHECK(t.numel() == numel, b.name, ": column/", what, " length mismatch");
+}
+
+// Cutoffs of the columns of one launch, flattened: column j's are
+// flat[offs[j] .. offs[j] + lens[j]); max_ncut >= 1 sizes the kernel's LDS.
+struct CutoffTable {
+  std::vector<double> flat;
+  std::vector<int64_t> offs;
+  std::vector<int> lens;
+  int max_ncut = 1;
+};
+
+CutoffTable cutoff_table(const std::vector<torch::Tensor> &cutoffs, const std::vector<int64_t> &idx) {
+  CutoffTable ct;
+  for (int64_t i : idx) {
+    auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
+    const double *cd = cc.data_ptr<double>();
+    ct.offs.push_back((int64_t)ct.flat.size());
+    ct.flat.insert(ct.flat.end(), cd, cd + cc.numel());
+    ct.lens.push_back((int)cc.numel());
+    ct.max_ncut = std::max(ct.max_ncut, (int)cc.numel());
+  }
+  return ct;
+}
+
+// K1/K2 (p < 0) and K1/K2+K4 fused (p >= 0: HLL registers from the same read).
+std::tuple<torch::Tensor, torch::Tensor> moments_body(const std::vector<torch::Tensor> &cols,
+                                                      const std::vector<double> &shifts,
+                                                      int64_t p, const char *name) {
+  ColumnBatch all = gather_columns(cols, name, F32 | F64);
+  if (!shifts.empty()) check_count(shifts.size(), cols.size(), name, "shifts");
+  auto device = all.device;
+  const bool hll = p >= 0;
+  const int64_t m = hll ? (int64_t)1 << p : 0;
+  auto mom = torch::zeros({all.ncols(), 9}, on(device, torch::kFloat64));
+  torch::Tensor regs, reg_sub;
+  if (hll) regs = torch::zeros({all.ncols(), m}, on(device, torch::kInt32));
+  for (auto &b : split_by_dtype(all)) {
+    int ncols = b.ncols();
+    int nchunks = pick_chunks(b.maxn, ncols);
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto dsh = upload(shifts.empty() ? std::vector<double>(ncols, 0.0) : pick(shifts, b.idx), device);
+    auto partials = torch::empty({(int64_t)ncols * nchunks, 9}, on(device, torch::kFloat64));
+    auto sub = torch::empty({ncols, 9}, on(device, torch::kFloat64));
+    if (hll) {
+      reg_sub = torch::zeros({ncols, m}, on(device, torch::kInt32));
+      check_hip(anovos_moments_hll(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
+                                   dsh.data_ptr<double>(), ncols, (int)p, nchunks, b.dtype,
+                                   partials.data_ptr<double>(), sub.data_ptr<double>(),
+                                   reg_sub.data_ptr<int>(), current_stream()),
+                "anovos_moments_hll");
+    } else {
+      check_hip(anovos_moments(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
+                               dsh.data_ptr<double>(), ncols, nchunks, b.dtype,
+                               partials.data_ptr<double>(), sub.data_ptr<double>(),
+                               current_stream()),
+                "anovos_moments");
+    }
+    auto didx = upload(b.idx, device);
+    mom.index_copy_(0, didx, sub);
+    if (hll) regs.index_copy_(0, didx, reg_sub);
+  }
+  return {mom, regs};
+}
+
+// K6 to float bin labels; with_counts adds int64 [ncols, max_ncut + 2] bin
+// counts from the same pass (slot 0 nulls, slot b = bin label b), in the
+// ORIGINAL column order, local to this rank, left on the device.
+std::tuple<std::vector<torch::Tensor>, torch::Tensor> bucketize_float_body(
+    const std::vector<torch::Tensor> &cols, const std::vector<torch::Tensor> &cutoffs,
+    bool with_counts, const char *name) {
+  ColumnBatch all = gather_columns(cols, name, F32 | F64);
+  check_count(cutoffs.size(), cols.size(), name, "cutoffs");
+  auto device = all.device;
+  int64_t stride = 2;
+  for (auto &c : cutoffs) {
+    TORCH_CHECK(!with_counts || c.numel() <= BKT_COUNTS_MAX_NCUT, name,
+                ": cutoff count out of LDS range");
+    stride = std::max<int64_t>(stride, c.numel() + 2);
+  }
+  std::vector<torch::Tensor> outs;
+  for (auto &t : cols) outs.push_back(torch::empty(t.sizes(), on(device, torch::kFloat32)));
+  torch::Tensor counts;
+  if (with_counts) counts = torch::zeros({all.ncols(), stride}, on(device, torch::kInt64));
+  for (auto &b : split_by_dtype(all)) {
+    CutoffTable ct = cutoff_table(cutoffs, b.idx);
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto dout = upload(out_ptrs(outs, b), device);
+    auto doff = upload(ct.offs, device);
+    auto dflat = upload(ct.flat, device);
+    auto dclen = upload(ct.lens, device);
+    if (with_counts) {
+      std::vector<int64_t> coffs;
+      for (int64_t i : b.idx) coffs.push_back(i * stride);
+      auto dcoff = upload(coffs, device);
+      check_hip(anovos_bucketize_float_counts(
+                    ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                    dflat.data_ptr<double>(), doff.data_ptr<int64_t>(), dclen.data_ptr<int>(),
+                    ct.max_ncut, nchunks, b.dtype, ptr_table<float>(dout),
+                    (uint64_t *)counts.data_ptr<int64_t>(), dcoff.data_ptr<int64_t>(),
+                    current_stream()),
+                "anovos_bucketize_float_counts");
+    } else {
+      check_hip(anovos_bucketize_float(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
+                                       b.ncols(), dflat.data_ptr<double>(),
+                                       doff.data_ptr<int64_t>(), dclen.data_ptr<int>(),
+                                       ct.max_ncut, nchunks, b.dtype, ptr_table<float>(dout),
+                                       current_stream()),
+                "anovos_bucketize_float");
+    }
+  }
+  return {outs, counts};
+}
+
+// K12: out = lut[code], one LUT per column, T = float or int32_t.
+template <typename T, typename Launcher>
+std::vector<torch::Tensor> lut_apply_body(const std::vector<torch::Tensor> &cols,
+                                          const std::vector<torch::Tensor> &luts,
+                                          Launcher launch, const char *name) {
+  ColumnBatch b = gather_columns(cols, name, I32);
+  check_count(luts.size(), cols.size(), name, "luts");
+  const auto st = c10::CppTypeToScalarType<T>::value;
+  std::vector<int64_t> offs;
+  std::vector<T> flat;
+  for (auto &l : luts) {
+    auto lc = l.to(st).cpu().contiguous();
+    offs.push_back((int64_t)flat.size());
+    flat.insert(flat.end(), lc.template data_ptr<T>(), lc.template data_ptr<T>() + lc.numel());
+  }
+  std::vector<torch::Tensor> outs;
+  for (auto &t : cols) outs.push_back(torch::empty(t.sizes(), on(b.device, st)));
+  int nchunks = pick_chunks(b.maxn, b.ncols());
+  auto dptr = upload(b.ptrs, b.device);
+  auto dlen = upload(b.lens, b.device);
+  auto dout = upload(out_ptrs(outs, b), b.device);
+  auto doff = upload(offs, b.device);
+  auto dflat = upload(flat, b.device);
+  check_hip(launch(ptr_table<const int32_t>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                   dflat.template data_ptr<T>(), doff.data_ptr<int64_t>(), nchunks,
+                   ptr_table<T>(dout), current_stream()),
+            name);
+  return outs;
 }
 
 }  // namespace
 
 torch::Tensor column_moments(std::vector<torch::Tensor> cols, std::vector<double> shifts) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(shifts.empty() || shifts.size() == cols.size(), "shifts must match cols");
-  auto device = cols[0].device();
-  auto out = torch::zeros({(int64_t)cols.size(), 9},
-                          torch::TensorOptions().dtype(torch::kFloat64).device(device));
-  // group by dtype, one fused launch per dtype
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, idx;
-    std::vector<double> sh;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      auto &t = cols[i];
-      TORCH_CHECK(t.is_contiguous() && t.device() == device, "columns must be contiguous, same device");
-      if (dtype_code(t) != pass) continue;
-      ptrs.push_back((int64_t)t.data_ptr());
-      lens.push_back(t.numel());
-      sh.push_back(shifts.empty() ? 0.0 : shifts[i]);
-      idx.push_back((int64_t)i);
-    }
-    if (ptrs.empty()) continue;
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dsh = to_device_f64(sh, device);
-    auto partials = torch::empty({(int64_t)ncols * nchunks, 9},
-                                 torch::TensorOptions().dtype(torch::kFloat64).device(device));
-    auto sub = torch::empty({ncols, 9}, torch::TensorOptions().dtype(torch::kFloat64).device(device));
-    check_hip(anovos_moments((const void *const *)dptr.data_ptr<int64_t>(),
-                             dlen.data_ptr<int64_t>(), dsh.data_ptr<double>(),
-                             ncols, nchunks, pass,
-                             partials.data_ptr<double>(), sub.data_ptr<double>(),
-                             current_stream()),
-              "anovos_moments");
-    auto didx = to_device_i64(idx, device);
-    out.index_copy_(0, didx, sub);
-  }
-  return out;
+  return std::get<0>(moments_body(cols, shifts, -1, "column_moments"));
+}
+
+// K1/K2+K4 fused: moments + HLL registers in one read.
+// Returns (moments [ncols,9] f64, regs [ncols, 1<<p] i32).
+std::tuple<torch::Tensor, torch::Tensor> moments_hll(std::vector<torch::Tensor> cols, int64_t p,
+                                                     std::vector<double> shifts) {
+  TORCH_CHECK(p >= 0, "moments_hll: p must not be negative");
+  return moments_body(cols, shifts, p, "moments_hll");
 }
 
 torch::Tensor column_histograms(std::vector<torch::Tensor> cols, torch::Tensor lo,
                                 torch::Tensor hi, int64_t nbins) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  check_cols(cols, device, "column_histograms");
-  auto lo_d = lo.to(torch::kFloat64).to(device);
-  auto hi_d = hi.to(torch::kFloat64).to(device);
-  auto out = torch::zeros({(int64_t)cols.size(), nbins},
-                          torch::TensorOptions().dtype(torch::kInt64).device(device));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, idx;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      idx.push_back((int64_t)i);
-    }
-    if (ptrs.empty()) continue;
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto didx_cpu = idx;
-    auto sub = torch::zeros({ncols, nbins}, torch::TensorOptions().dtype(torch::kInt64).device(device));
-    auto lo_sel = lo_d.index_select(0, to_device_i64(didx_cpu, device));
-    auto hi_sel = hi_d.index_select(0, to_device_i64(didx_cpu, device));
-    check_hip(anovos_hist((const void *const *)dptr.data_ptr<int64_t>(),
-                          dlen.data_ptr<int64_t>(), ncols, lo_sel.data_ptr<double>(),
-                          hi_sel.data_ptr<double>(), (int)nbins, nchunks, pass,
-                          (uint64_t *)sub.data_ptr<int64_t>(), current_stream()),
+  ColumnBatch all = gather_columns(cols, "column_histograms", F32 | F64);
+  auto device = all.device;
+  auto lo_d = device_f64(lo, cols.size(), all, "lo");
+  auto hi_d = device_f64(hi, cols.size(), all, "hi");
+  auto out = torch::zeros({all.ncols(), nbins}, on(device, torch::kInt64));
+  for (auto &b : split_by_dtype(all)) {
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto didx = upload(b.idx, device);
+    auto sub = torch::zeros({b.ncols(), nbins}, on(device, torch::kInt64));
+    auto lo_sel = lo_d.index_select(0, didx);
+    auto hi_sel = hi_d.index_select(0, didx);
+    check_hip(anovos_hist(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                          lo_sel.data_ptr<double>(), hi_sel.data_ptr<double>(), (int)nbins,
+                          nchunks, b.dtype, (uint64_t *)sub.data_ptr<int64_t>(),
+                          current_stream()),
               "anovos_hist");
-    out.index_copy_(0, to_device_i64(didx_cpu, device), sub);
+    out.index_copy_(0, didx, sub);
   }
   return out;
 }
 
 torch::Tensor bracket_histograms(std::vector<torch::Tensor> cols, torch::Tensor colidx,
                                  torch::Tensor lo, torch::Tensor hi, int64_t nbins) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  check_cols(cols, device, "bracket_histograms");
-  int dtype = dtype_code(cols[0]);
-  for (auto &t : cols) TORCH_CHECK(dtype_code(t) == dtype, "bracket_histograms: mixed dtypes unsupported");
-  std::vector<int64_t> ptrs, lens;
-  for (auto &t : cols) {
-    ptrs.push_back((int64_t)t.data_ptr());
-    lens.push_back(t.numel());
+  ColumnBatch b = gather_columns(cols, "bracket_histograms", F32 | F64);
+  TORCH_CHECK(b.dtype >= 0, "bracket_histograms: mixed dtypes unsupported");
+  auto ci_h = colidx.to(torch::kInt64).cpu().contiguous();
+  int nbrackets = (int)ci_h.numel();
+  for (int i = 0; i < nbrackets; ++i) {
+    int64_t c = ci_h.data_ptr<int64_t>()[i];
+    TORCH_CHECK(c >= 0 && c < b.ncols(), "bracket_histograms: colidx entry ", c, " outside [0, ",
+                b.ncols(), ")");
   }
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto ci = colidx.to(torch::kInt64).to(device);
-  auto lo_d = lo.to(torch::kFloat64).to(device);
-  auto hi_d = hi.to(torch::kFloat64).to(device);
-  int nbrackets = (int)ci.numel();
-  int64_t maxn = *std::max_element(lens.begin(), lens.end());
-  int nchunks = pick_chunks(maxn, nbrackets);
-  auto out = torch::zeros({nbrackets, nbins}, torch::TensorOptions().dtype(torch::kInt64).device(device));
-  check_hip(anovos_bracket_hist((const void *const *)dptr.data_ptr<int64_t>(),
-                                dlen.data_ptr<int64_t>(), ci.data_ptr<int64_t>(),
-                                nbrackets, lo_d.data_ptr<double>(), hi_d.data_ptr<double>(),
-                                (int)nbins, nchunks, dtype,
+  auto lo_d = device_f64(lo, nbrackets, b, "lo");
+  auto hi_d = device_f64(hi, nbrackets, b, "hi");
+  auto ci = ci_h.to(b.device);
+  auto dptr = upload(b.ptrs, b.device);
+  auto dlen = upload(b.lens, b.device);
+  int nchunks = pick_chunks(b.maxn, nbrackets);
+  auto out = torch::zeros({nbrackets, nbins}, on(b.device, torch::kInt64));
+  check_hip(anovos_bracket_hist(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
+                                ci.data_ptr<int64_t>(), nbrackets, lo_d.data_ptr<double>(),
+                                hi_d.data_ptr<double>(), (int)nbins, nchunks, b.dtype,
                                 (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
             "anovos_bracket_hist");
   return out;
@@ -264,204 +374,123 @@ torch::Tensor bracket_histograms(std::vector<torch::Tensor> cols, torch::Tensor 
 
 std::vector<torch::Tensor> bucketize_columns(std::vector<torch::Tensor> cols,
                                              std::vector<torch::Tensor> cutoffs) {
-  TORCH_CHECK(cols.size() == cutoffs.size(), "cols/cutoffs size mismatch");
-  auto device = cols[0].device();
-  check_cols(cols, device, "bucketize_columns");
+  ColumnBatch all = gather_columns(cols, "bucketize_columns", F32 | F64);
+  check_count(cutoffs.size(), cols.size(), all.name, "cutoffs");
+  auto device = all.device;
   std::vector<torch::Tensor> outs;
-  for (auto &t : cols)
-    outs.push_back(torch::empty_like(t, torch::TensorOptions().dtype(torch::kInt32).device(device)));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, optrs, offs;
-    std::vector<double> flat;
-    std::vector<int> clens;
-    int max_ncut = 1;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      optrs.push_back((int64_t)outs[i].data_ptr());
-      auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
-      offs.push_back((int64_t)flat.size());
-      const double *cd = cc.data_ptr<double>();
-      flat.insert(flat.end(), cd, cd + cc.numel());
-      clens.push_back((int)cc.numel());
-      max_ncut = std::max(max_ncut, (int)cc.numel());
-    }
-    if (ptrs.empty()) continue;
-    if (flat.empty()) flat.push_back(0.0);  // from_blob on empty data() segfaults
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dout = to_device_i64(optrs, device);
-    auto doff = to_device_i64(offs, device);
-    auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
-                                  torch::TensorOptions().dtype(torch::kFloat64))
-                     .clone()
-                     .to(device);
-    auto dclen = torch::from_blob(clens.data(), {(int64_t)clens.size()},
-                                  torch::TensorOptions().dtype(torch::kInt32))
-                     .clone()
-                     .to(device);
-    check_hip(anovos_bucketize((const void *const *)dptr.data_ptr<int64_t>(),
-                               dlen.data_ptr<int64_t>(), ncols, dflat.data_ptr<double>(),
-                               doff.data_ptr<int64_t>(), dclen.data_ptr<int>(), max_ncut,
-                               nchunks, pass, (int32_t *const *)dout.data_ptr<int64_t>(),
-                               current_stream()),
+  for (auto &t : cols) outs.push_back(torch::empty_like(t, on(device, torch::kInt32)));
+  for (auto &b : split_by_dtype(all)) {
+    CutoffTable ct = cutoff_table(cutoffs, b.idx);
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto dout = upload(out_ptrs(outs, b), device);
+    auto doff = upload(ct.offs, device);
+    auto dflat = upload(ct.flat, device);
+    auto dclen = upload(ct.lens, device);
+    check_hip(anovos_bucketize(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                               dflat.data_ptr<double>(), doff.data_ptr<int64_t>(),
+                               dclen.data_ptr<int>(), ct.max_ncut, nchunks, b.dtype,
+                               ptr_table<int32_t>(dout), current_stream()),
               "anovos_bucketize");
   }
   return outs;
 }
 
 torch::Tensor code_counts(torch::Tensor codes, int64_t size) {
-  TORCH_CHECK(codes.scalar_type() == torch::kInt32, "codes must be int32");
-  auto device = codes.device();
-  auto out = torch::zeros({std::max<int64_t>(size, 1)},
-                          torch::TensorOptions().dtype(torch::kInt64).device(device));
+  ColumnBatch b = gather_columns({codes}, "code_counts", I32);
+  TORCH_CHECK(size >= 0 && size < INT32_MAX, "code_counts: dictionary size out of range");
+  auto out = torch::zeros({std::max<int64_t>(size, 1)}, on(b.device, torch::kInt64));
   if (size == 0 || codes.numel() == 0) return out.narrow(0, 0, size);
   int nchunks = pick_chunks(codes.numel(), 1);
   nchunks = std::min(nchunks, 8192);
-  check_hip(anovos_code_counts(codes.data_ptr<int32_t>(), codes.numel(), (int)size,
-                               nchunks, (uint64_t *)out.data_ptr<int64_t>(),
-                               current_stream()),
+  check_hip(anovos_code_counts(codes.data_ptr<int32_t>(), codes.numel(), (int)size, nchunks,
+                               (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
             "anovos_code_counts");
   return out;
 }
 
 torch::Tensor hll_registers(torch::Tensor x, int64_t p) {
-  auto device = x.device();
-  check_cols({x}, device, "hll_registers");
-  auto regs = torch::zeros({(int64_t)1 << p},
-                           torch::TensorOptions().dtype(torch::kInt32).device(device));
+  ColumnBatch b = gather_columns({x}, "hll_registers", F32 | F64);
+  auto regs = torch::zeros({(int64_t)1 << p}, on(b.device, torch::kInt32));
   if (x.numel() == 0) return regs;
   int nchunks = std::min(pick_chunks(x.numel(), 1), 4096);
-  check_hip(anovos_hll(x.data_ptr(), x.numel(), (int)p, nchunks, dtype_code(x),
+  check_hip(anovos_hll(x.data_ptr(), x.numel(), (int)p, nchunks, b.dtype,
                        regs.data_ptr<int32_t>(), current_stream()),
             "anovos_hll");
   return regs;
 }
 
+// K10: adds every row's null count into `out`; accepts float32/float64
+// (NaN null) AND int32 dictionary codes (-1 null), one launch per dtype.
 void row_null_counts_num(std::vector<torch::Tensor> cols, torch::Tensor out) {
-  // accepts float32/float64 (NaN null) AND int32 dictionary codes (-1 null)
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(out.scalar_type() == torch::kInt32, "out must be int32");
-  auto device = cols[0].device();
-  for (int pass = 0; pass < 3; ++pass) {
-    std::vector<int64_t> ptrs;
-    for (auto &t : cols) {
-      int dc = (t.scalar_type() == torch::kInt32) ? 2 : dtype_code(t);
-      if (dc != pass) continue;
-      TORCH_CHECK(t.numel() == out.numel(), "column length mismatch");
-      TORCH_CHECK(t.is_contiguous(), "columns must be contiguous");
-      ptrs.push_back((int64_t)t.data_ptr());
-    }
-    if (ptrs.empty()) continue;
-    auto dptr = to_device_i64(ptrs, device);
-    check_hip(anovos_row_null((const void *const *)dptr.data_ptr<int64_t>(),
-                              (int)ptrs.size(), out.numel(), pass,
+  ColumnBatch all = gather_columns(cols, "row_null_counts_num", F32 | F64 | I32, /*equal_len=*/true);
+  check_dense_on_device(out, all, "out", torch::kInt32, all.maxn);
+  for (auto &b : split_by_dtype(all)) {
+    auto dptr = upload(b.ptrs, b.device);
+    check_hip(anovos_row_null(ptr_table<const void>(dptr), b.ncols(), out.numel(), b.dtype,
                               out.data_ptr<int32_t>(), current_stream()),
               "anovos_row_null");
   }
 }
 
 torch::Tensor hll_registers_multi(std::vector<torch::Tensor> cols, int64_t p) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  check_cols(cols, device, "hll_registers_multi");
-  auto regs = torch::zeros({(int64_t)cols.size(), (int64_t)1 << p},
-                           torch::TensorOptions().dtype(torch::kInt32).device(device));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, rptrs, idx;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      idx.push_back((int64_t)i);
-    }
-    if (ptrs.empty()) continue;
+  ColumnBatch all = gather_columns(cols, "hll_registers_multi", F32 | F64);
+  auto device = all.device;
+  auto regs = torch::zeros({all.ncols(), (int64_t)1 << p}, on(device, torch::kInt32));
+  for (auto &b : split_by_dtype(all)) {
     // contiguous sub-block trick: launch on a per-pass register buffer
-    auto sub = torch::zeros({(int64_t)ptrs.size(), (int64_t)1 << p},
-                            torch::TensorOptions().dtype(torch::kInt32).device(device));
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = std::max(1, std::min((int)((maxn + (1 << 20) - 1) >> 20), (int)(4096 / std::max<size_t>(ptrs.size(), 1) + 1)));
-    check_hip(anovos_hll_multi((const void *const *)dptr.data_ptr<int64_t>(),
-                               dlen.data_ptr<int64_t>(), (int)ptrs.size(), (int)p,
-                               nchunks, pass, sub.data_ptr<int32_t>(), current_stream()),
+    auto sub = torch::zeros({b.ncols(), (int64_t)1 << p}, on(device, torch::kInt32));
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    int nchunks = std::max(1, std::min((int)((b.maxn + (1 << 20) - 1) >> 20), 4096 / b.ncols() + 1));
+    check_hip(anovos_hll_multi(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                               (int)p, nchunks, b.dtype, sub.data_ptr<int32_t>(),
+                               current_stream()),
               "anovos_hll_multi");
-    regs.index_copy_(0, to_device_i64(idx, device), sub);
+    regs.index_copy_(0, upload(b.idx, device), sub);
   }
   return regs;
 }
 
-std::vector<torch::Tensor> scale_columns(std::vector<torch::Tensor> cols,
-                                         torch::Tensor a, torch::Tensor b) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  check_cols(cols, device, "scale_columns");
-  auto a_c = a.to(torch::kFloat64).cpu().contiguous();
-  auto b_c = b.to(torch::kFloat64).cpu().contiguous();
+std::vector<torch::Tensor> scale_columns(std::vector<torch::Tensor> cols, torch::Tensor a,
+                                         torch::Tensor b) {
+  ColumnBatch all = gather_columns(cols, "scale_columns", F32 | F64);
+  auto av = host_f64(a, cols.size(), all.name, "a");
+  auto bv = host_f64(b, cols.size(), all.name, "b");
+  auto device = all.device;
   std::vector<torch::Tensor> outs;
-  for (auto &t : cols)
-    outs.push_back(torch::empty(t.sizes(), torch::TensorOptions().dtype(torch::kFloat32).device(device)));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, optrs;
-    std::vector<double> av, bv;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      optrs.push_back((int64_t)outs[i].data_ptr());
-      av.push_back(a_c.data_ptr<double>()[i]);
-      bv.push_back(b_c.data_ptr<double>()[i]);
-    }
-    if (ptrs.empty()) continue;
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, (int)ptrs.size());
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dout = to_device_i64(optrs, device);
-    auto da = torch::from_blob(av.data(), {(int64_t)av.size()}, torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
-    auto db = torch::from_blob(bv.data(), {(int64_t)bv.size()}, torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
-    check_hip(anovos_axpb((const void *const *)dptr.data_ptr<int64_t>(),
-                          dlen.data_ptr<int64_t>(), (int)ptrs.size(),
-                          da.data_ptr<double>(), db.data_ptr<double>(), nchunks, pass,
-                          (float *const *)dout.data_ptr<int64_t>(), current_stream()),
+  for (auto &t : cols) outs.push_back(torch::empty(t.sizes(), on(device, torch::kFloat32)));
+  for (auto &g : split_by_dtype(all)) {
+    int nchunks = pick_chunks(g.maxn, g.ncols());
+    auto dptr = upload(g.ptrs, device);
+    auto dlen = upload(g.lens, device);
+    auto dout = upload(out_ptrs(outs, g), device);
+    auto da = upload(pick(av, g.idx), device);
+    auto db = upload(pick(bv, g.idx), device);
+    check_hip(anovos_axpb(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), g.ncols(),
+                          da.data_ptr<double>(), db.data_ptr<double>(), nchunks, g.dtype,
+                          ptr_table<float>(dout), current_stream()),
               "anovos_axpb");
   }
   return outs;
 }
 
 std::vector<torch::Tensor> fill_nan_columns(std::vector<torch::Tensor> cols, torch::Tensor fill) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  check_cols(cols, device, "fill_nan_columns");
-  auto f_c = fill.to(torch::kFloat64).cpu().contiguous();
+  ColumnBatch all = gather_columns(cols, "fill_nan_columns", F32 | F64);
+  auto fv = host_f64(fill, cols.size(), all.name, "fill");
+  auto device = all.device;
   std::vector<torch::Tensor> outs;
   for (auto &t : cols) outs.push_back(torch::empty_like(t));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, optrs;
-    std::vector<double> fv;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      optrs.push_back((int64_t)outs[i].data_ptr());
-      fv.push_back(f_c.data_ptr<double>()[i]);
-    }
-    if (ptrs.empty()) continue;
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, (int)ptrs.size());
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dout = to_device_i64(optrs, device);
-    auto df = torch::from_blob(fv.data(), {(int64_t)fv.size()}, torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
-    check_hip(anovos_fillnan((const void *const *)dptr.data_ptr<int64_t>(),
-                             dlen.data_ptr<int64_t>(), (int)ptrs.size(),
-                             df.data_ptr<double>(), nchunks, pass,
-                             (void *const *)dout.data_ptr<int64_t>(), current_stream()),
+  for (auto &b : split_by_dtype(all)) {
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto dout = upload(out_ptrs(outs, b), device);
+    auto df = upload(pick(fv, b.idx), device);
+    check_hip(anovos_fillnan(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                             df.data_ptr<double>(), nchunks, b.dtype, ptr_table<void>(dout),
+                             current_stream()),
               "anovos_fillnan");
   }
   return outs;
@@ -470,32 +499,18 @@ std::vector<torch::Tensor> fill_nan_columns(std::vector<torch::Tensor> cols, tor
 // Fused categorical null-fill: out_i = (code == -1) ? fill_i : code.
 std::vector<torch::Tensor> fill_code_columns(std::vector<torch::Tensor> cols,
                                              std::vector<int64_t> fills) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(fills.size() == cols.size(), "fills must match cols");
-  auto device = cols[0].device();
+  ColumnBatch b = gather_columns(cols, "fill_code_columns", I32);
+  check_count(fills.size(), cols.size(), b.name, "fills");
   std::vector<torch::Tensor> outs;
-  std::vector<int64_t> ptrs, lens, optrs;
-  std::vector<int64_t> fv;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    auto &t = cols[i];
-    TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_contiguous() && t.device() == device,
-                "expected contiguous int32 code columns on one device");
-    outs.push_back(torch::empty_like(t));
-    ptrs.push_back((int64_t)t.data_ptr());
-    lens.push_back(t.numel());
-    optrs.push_back((int64_t)outs.back().data_ptr());
-    fv.push_back(fills[i]);
-  }
-  int64_t maxn = *std::max_element(lens.begin(), lens.end());
-  int nchunks = pick_chunks(maxn, (int)ptrs.size());
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto dout = to_device_i64(optrs, device);
-  auto df64 = to_device_i64(fv, device).to(torch::kInt32);
-  check_hip(anovos_fill_code((const int32_t *const *)dptr.data_ptr<int64_t>(),
-                             dlen.data_ptr<int64_t>(), (int)ptrs.size(),
-                             df64.data_ptr<int32_t>(), nchunks,
-                             (int32_t *const *)dout.data_ptr<int64_t>(), current_stream()),
+  for (auto &t : cols) outs.push_back(torch::empty_like(t));
+  int nchunks = pick_chunks(b.maxn, b.ncols());
+  auto dptr = upload(b.ptrs, b.device);
+  auto dlen = upload(b.lens, b.device);
+  auto dout = upload(out_ptrs(outs, b), b.device);
+  auto dfill = upload(std::vector<int32_t>(fills.begin(), fills.end()), b.device);
+  check_hip(anovos_fill_code(ptr_table<const int32_t>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                             dfill.data_ptr<int32_t>(), nchunks, ptr_table<int32_t>(dout),
+                             current_stream()),
             "anovos_fill_code");
   return outs;
 }
@@ -505,275 +520,87 @@ torch::Tensor bracket_histograms_grouped(std::vector<torch::Tensor> cols,
                                          torch::Tensor lo, torch::Tensor hi,
                                          torch::Tensor p1lo, torch::Tensor p1scale,
                                          int64_t p1bins) {
-  // brackets MUST be sorted by column index; returns [nbrackets, 512].
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  check_cols(cols, device, "bracket_histograms_grouped");
+  // brackets MUST be sorted by column index; returns [nbrackets, RB_BINS].
+  ColumnBatch b = gather_columns(cols, "bracket_histograms_grouped", F32 | F64);
   auto bc = bracket_col.to(torch::kInt64).cpu().contiguous();
+  const int64_t *bcol = bc.data_ptr<int64_t>();
+  int ncols = b.ncols();
+  int nb = (int)bc.numel();
   // dtype uniformity only matters for REFERENCED columns (the host
   // splits mixed-dtype bracket sets into per-dtype launches; columns
   // without brackets in this launch are never read)
   int dtype = -1;
-  {
-    const int64_t *b = bc.data_ptr<int64_t>();
-    for (int i = 0; i < (int)bc.numel(); ++i) {
-      TORCH_CHECK(b[i] >= 0 && b[i] < (int64_t)cols.size(), "bad bracket col");
-      int d = dtype_code(cols[b[i]]);
-      if (dtype < 0) dtype = d;
-      TORCH_CHECK(d == dtype, "grouped brackets: mixed dtypes in one launch");
-    }
-    if (dtype < 0) dtype = dtype_code(cols[0]);
-  }
-  int ncols = (int)cols.size();
-  int nb = (int)bc.numel();
   std::vector<int> bstart(ncols + 1, 0);
-  {
-    const int64_t *b = bc.data_ptr<int64_t>();
-    for (int i = 0; i < nb; ++i) {
-      TORCH_CHECK(b[i] >= 0 && b[i] < ncols, "bad bracket col");
-      if (i) TORCH_CHECK(b[i] >= b[i - 1], "brackets must be sorted by column");
-      bstart[b[i] + 1]++;
-    }
-    for (int c = 0; c < ncols; ++c) {
-      TORCH_CHECK(bstart[c + 1] <= 16, "at most 16 brackets per column");
-      bstart[c + 1] += bstart[c];
-    }
+  for (int i = 0; i < nb; ++i) {
+    TORCH_CHECK(bcol[i] >= 0 && bcol[i] < ncols, b.name, ": bad bracket col");
+    if (i) TORCH_CHECK(bcol[i] >= bcol[i - 1], b.name, ": brackets must be sorted by column");
+    if (dtype < 0) dtype = b.dtypes[bcol[i]];
+    TORCH_CHECK(b.dtypes[bcol[i]] == dtype, "grouped brackets: mixed dtypes in one launch");
+    bstart[bcol[i] + 1]++;
   }
-  std::vector<int64_t> ptrs, lens;
-  for (auto &t : cols) {
-    ptrs.push_back((int64_t)t.data_ptr());
-    lens.push_back(t.numel());
+  if (dtype < 0) dtype = b.dtypes[0];
+  for (int c = 0; c < ncols; ++c) {
+    TORCH_CHECK(bstart[c + 1] <= RB_MAXB, b.name, ": at most 16 brackets per column");
+    bstart[c + 1] += bstart[c];
   }
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto dbs = torch::from_blob(bstart.data(), {(int64_t)bstart.size()}, torch::TensorOptions().dtype(torch::kInt32)).clone().to(device);
-  auto lo_d = lo.to(torch::kFloat64).to(device);
-  auto hi_d = hi.to(torch::kFloat64).to(device);
-  auto p1lo_d = p1lo.to(torch::kFloat64).to(device).contiguous();
-  auto p1scale_d = p1scale.to(torch::kFloat64).to(device).contiguous();
-  int64_t maxn = *std::max_element(lens.begin(), lens.end());
-  int nchunks = pick_chunks(maxn, ncols);
-  auto out = torch::zeros({nb, 512}, torch::TensorOptions().dtype(torch::kInt64).device(device));
-  check_hip(anovos_bracket_hist_grouped((const void *const *)dptr.data_ptr<int64_t>(),
-                                        dlen.data_ptr<int64_t>(), dbs.data_ptr<int>(), ncols,
-                                        lo_d.data_ptr<double>(), hi_d.data_ptr<double>(),
-                                        p1lo_d.data_ptr<double>(), p1scale_d.data_ptr<double>(),
-                                        (int)p1bins, nchunks, dtype,
-                                        (uint64_t *)out.data_ptr<int64_t>(),
-                                        current_stream()),
+  auto lo_d = device_f64(lo, nb, b, "lo");
+  auto hi_d = device_f64(hi, nb, b, "hi");
+  auto p1lo_d = device_f64(p1lo, ncols, b, "p1lo");
+  auto p1scale_d = device_f64(p1scale, ncols, b, "p1scale");
+  auto dptr = upload(b.ptrs, b.device);
+  auto dlen = upload(b.lens, b.device);
+  auto dbs = upload(bstart, b.device);
+  int nchunks = pick_chunks(b.maxn, ncols);
+  auto out = torch::zeros({nb, RB_BINS}, on(b.device, torch::kInt64));
+  check_hip(anovos_bracket_hist_grouped(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
+                                        dbs.data_ptr<int>(), ncols, lo_d.data_ptr<double>(),
+                                        hi_d.data_ptr<double>(), p1lo_d.data_ptr<double>(),
+                                        p1scale_d.data_ptr<double>(), (int)p1bins, nchunks, dtype,
+                                        (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
             "anovos_bracket_hist_grouped");
   return out;
 }
 
 std::vector<torch::Tensor> bucketize_columns_float(std::vector<torch::Tensor> cols,
                                                    std::vector<torch::Tensor> cutoffs) {
-  TORCH_CHECK(cols.size() == cutoffs.size(), "cols/cutoffs size mismatch");
-  auto device = cols[0].device();
-  check_cols(cols, device, "bucketize_columns_float");
-  std::vector<torch::Tensor> outs;
-  for (auto &t : cols)
-    outs.push_back(torch::empty(t.sizes(), torch::TensorOptions().dtype(torch::kFloat32).device(device)));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, optrs, offs;
-    std::vector<double> flat;
-    std::vector<int> clens;
-    int max_ncut = 1;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      optrs.push_back((int64_t)outs[i].data_ptr());
-      auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
-      offs.push_back((int64_t)flat.size());
-      const double *cd = cc.data_ptr<double>();
-      flat.insert(flat.end(), cd, cd + cc.numel());
-      clens.push_back((int)cc.numel());
-      max_ncut = std::max(max_ncut, (int)cc.numel());
-    }
-    if (ptrs.empty()) continue;
-    if (flat.empty()) flat.push_back(0.0);  // from_blob on empty data() segfaults
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dout = to_device_i64(optrs, device);
-    auto doff = to_device_i64(offs, device);
-    auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
-                                  torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
-    auto dclen = torch::from_blob(clens.data(), {(int64_t)clens.size()},
-                                  torch::TensorOptions().dtype(torch::kInt32)).clone().to(device);
-    check_hip(anovos_bucketize_float((const void *const *)dptr.data_ptr<int64_t>(),
-                                     dlen.data_ptr<int64_t>(), ncols, dflat.data_ptr<double>(),
-                                     doff.data_ptr<int64_t>(), dclen.data_ptr<int>(), max_ncut,
-                                     nchunks, pass, (float *const *)dout.data_ptr<int64_t>(),
-                                     current_stream()),
-              "anovos_bucketize_float");
-  }
-  return outs;
+  return std::get<0>(bucketize_float_body(cols, cutoffs, false, "bucketize_columns_float"));
 }
 
-// K6 with counts: same outputs as bucketize_columns_float plus per-column
-// bin counts from the same pass. counts is int64 [ncols, max_ncut + 2] in
-// the ORIGINAL column order (slot 0 nulls, slot b = bin label b), local to
-// this rank, left on the device.
 std::tuple<std::vector<torch::Tensor>, torch::Tensor> bucketize_columns_float_counts(
     std::vector<torch::Tensor> cols, std::vector<torch::Tensor> cutoffs) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(cols.size() == cutoffs.size(), "cols/cutoffs size mismatch");
-  auto device = cols[0].device();
-  std::vector<torch::Tensor> outs;
-  int64_t stride = 2;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    TORCH_CHECK(cols[i].is_contiguous() && cols[i].device() == device,
-                "columns must be contiguous, same device");
-    TORCH_CHECK(cutoffs[i].numel() <= 4096, "cutoff count out of LDS range");
-    outs.push_back(torch::empty(cols[i].sizes(), torch::TensorOptions().dtype(torch::kFloat32).device(device)));
-    stride = std::max<int64_t>(stride, cutoffs[i].numel() + 2);
-  }
-  auto counts = torch::zeros({(int64_t)cols.size(), stride},
-                             torch::TensorOptions().dtype(torch::kInt64).device(device));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, optrs, offs, coffs;
-    std::vector<double> flat;
-    std::vector<int> clens;
-    int max_ncut = 1;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      optrs.push_back((int64_t)outs[i].data_ptr());
-      coffs.push_back((int64_t)i * stride);
-      auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
-      offs.push_back((int64_t)flat.size());
-      const double *cd = cc.data_ptr<double>();
-      flat.insert(flat.end(), cd, cd + cc.numel());
-      clens.push_back((int)cc.numel());
-      max_ncut = std::max(max_ncut, (int)cc.numel());
-    }
-    if (ptrs.empty()) continue;
-    if (flat.empty()) flat.push_back(0.0);  // from_blob on empty data() segfaults
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dout = to_device_i64(optrs, device);
-    auto doff = to_device_i64(offs, device);
-    auto dcoff = to_device_i64(coffs, device);
-    auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
-                                  torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
-    auto dclen = torch::from_blob(clens.data(), {(int64_t)clens.size()},
-                                  torch::TensorOptions().dtype(torch::kInt32)).clone().to(device);
-    check_hip(anovos_bucketize_float_counts(
-                  (const void *const *)dptr.data_ptr<int64_t>(), dlen.data_ptr<int64_t>(), ncols,
-                  dflat.data_ptr<double>(), doff.data_ptr<int64_t>(), dclen.data_ptr<int>(),
-                  max_ncut, nchunks, pass, (float *const *)dout.data_ptr<int64_t>(),
-                  (uint64_t *)counts.data_ptr<int64_t>(), dcoff.data_ptr<int64_t>(),
-                  current_stream()),
-              "anovos_bucketize_float_counts");
-  }
-  return {outs, counts};
+  return bucketize_float_body(cols, cutoffs, true, "bucketize_columns_float_counts");
 }
 
 std::vector<torch::Tensor> lut_apply_f32(std::vector<torch::Tensor> cols,
                                          std::vector<torch::Tensor> luts) {
-  TORCH_CHECK(cols.size() == luts.size(), "cols/luts size mismatch");
-  auto device = cols[0].device();
-  check_cols(cols, device, "lut_apply_f32");
-  std::vector<int64_t> ptrs, lens, optrs, offs;
-  std::vector<float> flat;
-  std::vector<torch::Tensor> outs;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    TORCH_CHECK(cols[i].scalar_type() == torch::kInt32, "codes must be int32");
-    outs.push_back(torch::empty(cols[i].sizes(), torch::TensorOptions().dtype(torch::kFloat32).device(device)));
-    ptrs.push_back((int64_t)cols[i].data_ptr());
-    lens.push_back(cols[i].numel());
-    optrs.push_back((int64_t)outs[i].data_ptr());
-    auto lc = luts[i].to(torch::kFloat32).cpu().contiguous();
-    offs.push_back((int64_t)flat.size());
-    const float *ld = lc.data_ptr<float>();
-    flat.insert(flat.end(), ld, ld + lc.numel());
-  }
-  int64_t maxn = *std::max_element(lens.begin(), lens.end());
-  int nchunks = pick_chunks(maxn, (int)cols.size());
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto dout = to_device_i64(optrs, device);
-  auto doff = to_device_i64(offs, device);
-  auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
-                                torch::TensorOptions().dtype(torch::kFloat32)).clone().to(device);
-  check_hip(anovos_lut_apply_f32((const int32_t *const *)dptr.data_ptr<int64_t>(),
-                                 dlen.data_ptr<int64_t>(), (int)cols.size(),
-                                 dflat.data_ptr<float>(), doff.data_ptr<int64_t>(), nchunks,
-                                 (float *const *)dout.data_ptr<int64_t>(), current_stream()),
-            "anovos_lut_apply_f32");
-  return outs;
+  return lut_apply_body<float>(cols, luts, anovos_lut_apply_f32, "lut_apply_f32");
 }
 
 std::vector<torch::Tensor> lut_apply_i32(std::vector<torch::Tensor> cols,
                                          std::vector<torch::Tensor> luts) {
-  TORCH_CHECK(cols.size() == luts.size(), "cols/luts size mismatch");
-  auto device = cols[0].device();
-  check_cols(cols, device, "lut_apply_i32");
-  std::vector<int64_t> ptrs, lens, optrs, offs;
-  std::vector<int32_t> flat;
-  std::vector<torch::Tensor> outs;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    TORCH_CHECK(cols[i].scalar_type() == torch::kInt32, "codes must be int32");
-    outs.push_back(torch::empty(cols[i].sizes(), torch::TensorOptions().dtype(torch::kInt32).device(device)));
-    ptrs.push_back((int64_t)cols[i].data_ptr());
-    lens.push_back(cols[i].numel());
-    optrs.push_back((int64_t)outs[i].data_ptr());
-    auto lc = luts[i].to(torch::kInt32).cpu().contiguous();
-    offs.push_back((int64_t)flat.size());
-    const int32_t *ld = lc.data_ptr<int32_t>();
-    flat.insert(flat.end(), ld, ld + lc.numel());
-  }
-  int64_t maxn = *std::max_element(lens.begin(), lens.end());
-  int nchunks = pick_chunks(maxn, (int)cols.size());
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto dout = to_device_i64(optrs, device);
-  auto doff = to_device_i64(offs, device);
-  auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
-                                torch::TensorOptions().dtype(torch::kInt32)).clone().to(device);
-  check_hip(anovos_lut_apply_i32((const int32_t *const *)dptr.data_ptr<int64_t>(),
-                                 dlen.data_ptr<int64_t>(), (int)cols.size(),
-                                 dflat.data_ptr<int32_t>(), doff.data_ptr<int64_t>(), nchunks,
-                                 (int32_t *const *)dout.data_ptr<int64_t>(), current_stream()),
-            "anovos_lut_apply_i32");
-  return outs;
+  return lut_apply_body<int32_t>(cols, luts, anovos_lut_apply_i32, "lut_apply_i32");
 }
-
 
 // K8: bf16 MFMA centered Gram — gram[i][j] = sum (x_i - mean_i)(x_j - mean_j)
 torch::Tensor centered_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor means) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  const int k = (int)cols.size();
-  std::vector<int64_t> ptrs;
-  int64_t n = cols[0].numel();
-  for (auto &t : cols) {
-    TORCH_CHECK(t.is_contiguous() && t.device() == device, "columns must be contiguous, same device");
-    TORCH_CHECK(t.scalar_type() == torch::kFloat32, "centered_gram_bf16 expects float32 columns");
-    TORCH_CHECK(t.numel() == n, "all columns must have equal length");
-    ptrs.push_back((int64_t)t.data_ptr());
-  }
+  ColumnBatch b = gather_columns(cols, "centered_gram_bf16", F32, /*equal_len=*/true);
+  check_count((size_t)means.numel(), cols.size(), b.name, "means");
+  auto device = b.device;
+  const int k = b.ncols();
+  const int64_t n = b.maxn;
   auto means_d = means.to(device, torch::kFloat32).contiguous();
-  TORCH_CHECK(means_d.numel() == k, "means length mismatch");
   const int kt = (k + 15) / 16;
-  std::vector<int64_t> pi64, pj64;
+  std::vector<int> pi_h, pj_h;
   for (int i = 0; i < kt; ++i)
     for (int j = i; j < kt; ++j) {
-      pi64.push_back(i);
-      pj64.push_back(j);
+      pi_h.push_back(i);
+      pj_h.push_back(j);
     }
-  const int npairs = (int)pi64.size();
-  auto pi = to_device_i64(pi64, device).to(torch::kInt32);
-  auto pj = to_device_i64(pj64, device).to(torch::kInt32);
-  auto dptr = to_device_i64(ptrs, device);
-  auto gram = torch::zeros({k, k}, torch::TensorOptions().dtype(torch::kFloat32).device(device));
+  const int npairs = (int)pi_h.size();
+  auto pi = upload(pi_h, device);
+  auto pj = upload(pj_h, device);
+  auto dptr = upload(b.ptrs, device);
+  auto gram = torch::zeros({k, k}, on(device, torch::kFloat32));
   if (kt <= 13) {
     // single-read kernel: one block stages 128-row macro-slabs of ALL
     // columns through LDS; HBM traffic = n*k*4 bytes (vs ~kt x for
@@ -785,11 +612,9 @@ torch::Tensor centered_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
     int64_t target_chunks = anovos_gram_sr_grid(k);
     if (const char *e = getenv("ANOVOS_GRAM_CHUNKS")) target_chunks = atoll(e);
     int row_chunks = (int)std::min<int64_t>(target_chunks, std::max<int64_t>(1, steps_total));
-    auto partials = torch::empty({(int64_t)row_chunks * npairs, 256},
-                                 torch::TensorOptions().dtype(torch::kFloat32).device(device));
-    check_hip(anovos_centered_gram_sr((const void *const *)dptr.data_ptr<int64_t>(), n, k,
-                                      means_d.data_ptr<float>(), pi.data_ptr<int>(),
-                                      pj.data_ptr<int>(), npairs, row_chunks,
+    auto partials = torch::empty({(int64_t)row_chunks * npairs, 256}, on(device, torch::kFloat32));
+    check_hip(anovos_centered_gram_sr(ptr_table<const void>(dptr), n, k, means_d.data_ptr<float>(),
+                                      pi.data_ptr<int>(), pj.data_ptr<int>(), npairs, row_chunks,
                                       partials.data_ptr<float>(), gram.data_ptr<float>(),
                                       current_stream()),
               "anovos_centered_gram_sr");
@@ -800,70 +625,53 @@ torch::Tensor centered_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
   int row_chunks = (int)std::min<int64_t>(std::max<int64_t>(1, 2048 / std::max(npairs, 1)),
                                           std::max<int64_t>(1, n >> 16));
   row_chunks = std::max(row_chunks, 1);
-  auto partials = torch::empty({(int64_t)npairs * row_chunks, 256},
-                               torch::TensorOptions().dtype(torch::kFloat32).device(device));
-  check_hip(anovos_centered_gram((const void *const *)dptr.data_ptr<int64_t>(), n, k,
-                                 means_d.data_ptr<float>(), pi.data_ptr<int>(),
-                                 pj.data_ptr<int>(), npairs, row_chunks,
+  auto partials = torch::empty({(int64_t)npairs * row_chunks, 256}, on(device, torch::kFloat32));
+  check_hip(anovos_centered_gram(ptr_table<const void>(dptr), n, k, means_d.data_ptr<float>(),
+                                 pi.data_ptr<int>(), pj.data_ptr<int>(), npairs, row_chunks,
                                  partials.data_ptr<float>(), gram.data_ptr<float>(),
                                  current_stream()),
             "anovos_centered_gram");
   return gram;
 }
 
-
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1).
 torch::Tensor code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int64_t> sizes) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(cols.size() == sizes.size(), "sizes mismatch");
-  auto device = cols[0].device();
-  std::vector<int64_t> ptrs, lens, offs;
-  std::vector<int64_t> sz64;
-  int64_t off = 0, maxn = 0;
+  ColumnBatch b = gather_columns(cols, "code_counts_multi", I32);
+  check_count(sizes.size(), cols.size(), b.name, "sizes");
+  std::vector<int64_t> offs;
+  int64_t off = 0;
   // the kernel stages a column's counters in LDS when its slots (codes +
-  // null slot) number <= 16384 and counts in global memory otherwise, per
-  // column: size the LDS for the largest column that stages, not for the
-  // largest column of the launch
+  // null slot) number <= CODE_LDS_SLOTS and counts in global memory
+  // otherwise, per column: size the LDS for the largest column that
+  // stages, not for the largest column of the launch
   int lds_slots = 0;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    auto &t = cols[i];
-    TORCH_CHECK(t.is_contiguous() && t.scalar_type() == torch::kInt32, "int32 code columns required");
-    TORCH_CHECK(sizes[i] >= 0 && sizes[i] < INT32_MAX, "dictionary size out of range");
-    ptrs.push_back((int64_t)t.data_ptr());
-    lens.push_back(t.numel());
-    maxn = std::max(maxn, t.numel());
+  for (int64_t s : sizes) {
+    TORCH_CHECK(s >= 0 && s < INT32_MAX, b.name, ": dictionary size out of range");
     offs.push_back(off);
-    off += sizes[i] + 1;
-    sz64.push_back(sizes[i]);
-    if (sizes[i] + 1 <= 16384) lds_slots = std::max(lds_slots, (int)sizes[i] + 1);
+    off += s + 1;
+    if (s + 1 <= CODE_LDS_SLOTS) lds_slots = std::max(lds_slots, (int)s + 1);
   }
-  int ncols = (int)cols.size();
-  int nchunks = pick_chunks(maxn, ncols);
-  auto out = torch::zeros({off}, torch::TensorOptions().dtype(torch::kInt64).device(device));
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto doff = to_device_i64(offs, device);
-  auto dsz = to_device_i64(sz64, device).to(torch::kInt32);
-  check_hip(anovos_code_counts_multi((const int32_t *const *)dptr.data_ptr<int64_t>(),
-                                     dlen.data_ptr<int64_t>(), doff.data_ptr<int64_t>(),
-                                     dsz.data_ptr<int>(), ncols, lds_slots, nchunks,
-                                     (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
+  int nchunks = pick_chunks(b.maxn, b.ncols());
+  auto out = torch::zeros({off}, on(b.device, torch::kInt64));
+  auto dptr = upload(b.ptrs, b.device);
+  auto dlen = upload(b.lens, b.device);
+  auto doff = upload(offs, b.device);
+  auto dsz = upload(std::vector<int>(sizes.begin(), sizes.end()), b.device);
+  check_hip(anovos_code_counts_multi(ptr_table<const int32_t>(dptr), dlen.data_ptr<int64_t>(),
+                                     doff.data_ptr<int64_t>(), dsz.data_ptr<int>(), b.ncols(),
+                                     lds_slots, nchunks, (uint64_t *)out.data_ptr<int64_t>(),
+                                     current_stream()),
             "anovos_code_counts_multi");
   return out;
 }
 
 // K22: contingency tables of column pairs. The kernel (pair_counts.hip)
-// takes work items "anchor column + up to kPairPmax partners"; the three
-// constants mirror PAIR_PMAX / PAIR_LDS_SLOTS / PAIR_ITEM_WORDS there.
+// takes work items "anchor column + up to PAIR_PMAX partners".
 namespace {
 
-constexpr int kPairPmax = 8;
-constexpr int64_t kPairLdsSlots = 16384;
-constexpr int kPairItemWords = 4 + 4 * kPairPmax;
-
 struct PairPlan {
-  std::vector<int64_t> items;  // kPairItemWords words per item
+  std::vector<int64_t> items;  // PAIR_ITEM_WORDS words per item
   std::vector<int64_t> offs;   // output offset of every pair's table
   int64_t total = 0;           // cells of all tables
   int nitems = 0;
@@ -873,7 +681,7 @@ struct PairPlan {
 
 // Pairs are grouped by their first column (the anchor, in order of first
 // appearance) and packed greedily in pair order: an item closes when it
-// has kPairPmax partners or the next table would not fit the LDS budget.
+// has PAIR_PMAX partners or the next table would not fit the LDS budget.
 // A table with more cells than the budget is an item of its own that
 // counts in global memory, so it never sizes the launch's LDS.
 PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<int64_t> &pair_i,
@@ -893,15 +701,15 @@ PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<in
     plan.total += (sizes[pair_i[q]] + 1) * (sizes[pair_j[q]] + 1);
   }
   auto open_item = [&](int64_t a) {
-    plan.items.resize(plan.items.size() + kPairItemWords, 0);
-    int64_t *it = plan.items.data() + (int64_t)plan.nitems * kPairItemWords;
+    plan.items.resize(plan.items.size() + PAIR_ITEM_WORDS, 0);
+    int64_t *it = plan.items.data() + (int64_t)plan.nitems * PAIR_ITEM_WORDS;
     it[0] = a;
     it[1] = sizes[a];
     plan.nitems += 1;
     plan.col_reads += 1;
   };
   auto add_partner = [&](int64_t q, int64_t lds_off) {
-    int64_t *it = plan.items.data() + (int64_t)(plan.nitems - 1) * kPairItemWords;
+    int64_t *it = plan.items.data() + (int64_t)(plan.nitems - 1) * PAIR_ITEM_WORDS;
     int64_t *pp = it + 4 + 4 * it[2];
     pp[0] = pair_j[q];
     pp[1] = sizes[pair_j[q]];
@@ -916,7 +724,7 @@ PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<in
     bool open = false;
     for (int64_t q : by_anchor[a]) {
       const int64_t cells = (sizes[a] + 1) * (sizes[pair_j[q]] + 1);
-      if (cells > kPairLdsSlots) {
+      if (cells > PAIR_LDS_SLOTS) {
         // word 3 stays 0: global-atomic item; the items are appended in
         // order, so it also closes the staged item that was open
         open_item(a);
@@ -924,7 +732,7 @@ PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<in
         open = false;
         continue;
       }
-      if (!open || nparts == kPairPmax || used + cells > kPairLdsSlots) {
+      if (!open || nparts == PAIR_PMAX || used + cells > PAIR_LDS_SLOTS) {
         open_item(a);
         open = true;
         used = 0;
@@ -933,7 +741,7 @@ PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<in
       add_partner(q, used);
       used += cells;
       nparts += 1;
-      plan.items[(int64_t)(plan.nitems - 1) * kPairItemWords + 3] = used;
+      plan.items[(int64_t)(plan.nitems - 1) * PAIR_ITEM_WORDS + 3] = used;
       plan.lds_slots = std::max(plan.lds_slots, (int)used);
     }
   }
@@ -947,20 +755,12 @@ PairPlan plan_pair_items(const std::vector<int64_t> &sizes, const std::vector<in
 // [0, size)) is each table's last row / last column.
 torch::Tensor pair_code_counts(std::vector<torch::Tensor> cols, std::vector<int64_t> sizes,
                                std::vector<int64_t> pair_i, std::vector<int64_t> pair_j) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(cols.size() == sizes.size(), "sizes mismatch");
-  auto device = cols[0].device();
-  TORCH_CHECK(device.is_cuda(), "pair_code_counts: device columns required");
-  check_cols(cols, device, "pair_code_counts");
-  const int64_t n = cols[0].numel();
-  std::vector<int64_t> ptrs;
-  for (auto &t : cols) {
-    TORCH_CHECK(t.scalar_type() == torch::kInt32, "int32 code columns required");
-    TORCH_CHECK(t.dim() == 1 && t.numel() == n, "columns must be 1-D and of equal length");
-    ptrs.push_back((int64_t)t.data_ptr());
-  }
+  ColumnBatch b = gather_columns(cols, "pair_code_counts", I32, /*equal_len=*/true);
+  check_count(sizes.size(), cols.size(), b.name, "sizes");
+  for (auto &t : cols) TORCH_CHECK(t.dim() == 1, "pair_code_counts: columns must be 1-D");
+  const int64_t n = b.maxn;
   PairPlan plan = plan_pair_items(sizes, pair_i, pair_j);
-  auto out = torch::zeros({plan.total}, torch::TensorOptions().dtype(torch::kInt64).device(device));
+  auto out = torch::zeros({plan.total}, on(b.device, torch::kInt64));
   if (n == 0 || plan.nitems == 0) return out;
   int nchunks = pick_chunks(n, plan.nitems);
   // chunk length a multiple of 4 rows: every chunk then starts at the same
@@ -969,12 +769,11 @@ torch::Tensor pair_code_counts(std::vector<torch::Tensor> cols, std::vector<int6
   // a staged counter holds at most one block's rows
   TORCH_CHECK(per <= (int64_t)UINT32_MAX, "rows per block exceed the 32-bit LDS counters");
   TORCH_CHECK((int64_t)plan.nitems * nchunks <= (int64_t)INT32_MAX, "grid too large");
-  auto dptr = to_device_i64(ptrs, device);
-  auto ditems = to_device_i64(plan.items, device);
-  check_hip(anovos_pair_code_counts((const int32_t *const *)dptr.data_ptr<int64_t>(),
-                                    ditems.data_ptr<int64_t>(), plan.nitems, n, per, nchunks,
-                                    plan.lds_slots, (uint64_t *)out.data_ptr<int64_t>(),
-                                    current_stream()),
+  auto dptr = upload(b.ptrs, b.device);
+  auto ditems = upload(plan.items, b.device);
+  check_hip(anovos_pair_code_counts(ptr_table<const int32_t>(dptr), ditems.data_ptr<int64_t>(),
+                                    plan.nitems, n, per, nchunks, plan.lds_slots,
+                                    (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
             "anovos_pair_code_counts");
   return out;
 }
@@ -990,49 +789,34 @@ std::vector<int64_t> pair_code_counts_plan(std::vector<int64_t> sizes, std::vect
 // K9 fused: label-conditioned histograms, ALL columns in one launch.
 // Per column at out[off]: [slots] totals then [slots] event counts.
 // Column dtype drives the slot mapping (f32 binned vs int32 codes).
-torch::Tensor label_counts_multi(std::vector<torch::Tensor> cols,
-                                 torch::Tensor label,
+torch::Tensor label_counts_multi(std::vector<torch::Tensor> cols, torch::Tensor label,
                                  std::vector<int64_t> sizes) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(cols.size() == sizes.size(), "sizes mismatch");
-  TORCH_CHECK(label.is_contiguous() && label.scalar_type() == torch::kUInt8,
-              "uint8 label required");
-  auto device = cols[0].device();
-  std::vector<int64_t> ptrs, lens, offs, dt, sz;
-  int64_t off = 0, maxn = 0;
+  ColumnBatch b = gather_columns(cols, "label_counts_multi", F32 | I32, /*equal_len=*/true);
+  check_count(sizes.size(), cols.size(), b.name, "sizes");
+  check_dense_on_device(label, b, "label", torch::kUInt8, b.maxn);
+  std::vector<int64_t> offs;
+  std::vector<int> kinds;  // the kernel's own code: 0 f32 binned, 1 int32 codes
+  int64_t off = 0;
   int max_slots = 0;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    auto &t = cols[i];
-    TORCH_CHECK(t.is_contiguous(), "contiguous columns required");
-    int dtype;
-    if (t.scalar_type() == torch::kFloat) dtype = 0;
-    else if (t.scalar_type() == torch::kInt) dtype = 1;
-    else TORCH_CHECK(false, "f32 or int32 columns required");
-    TORCH_CHECK(t.numel() == label.numel(), "column/label length mismatch");
-    TORCH_CHECK(sizes[i] >= 1 && sizes[i] <= 8192, "slot count out of LDS range");
-    ptrs.push_back((int64_t)t.data_ptr());
-    lens.push_back(t.numel());
+  for (int i = 0; i < b.ncols(); ++i) {
+    TORCH_CHECK(sizes[i] >= 1 && sizes[i] <= LABEL_MAX_SLOTS, b.name, ": slot count out of LDS range");
     offs.push_back(off);
     off += 2 * sizes[i];
-    dt.push_back(dtype);
-    sz.push_back(sizes[i]);
-    maxn = std::max(maxn, t.numel());
+    kinds.push_back(b.dtypes[i] == 2 ? 1 : 0);
     max_slots = std::max(max_slots, (int)sizes[i]);
   }
-  int ncols = (int)cols.size();
-  int nchunks = pick_chunks(maxn, ncols);
-  auto out = torch::zeros({off}, torch::TensorOptions().dtype(torch::kInt64).device(device));
-  auto dptr = to_device_i64(ptrs, device);
-  auto dlen = to_device_i64(lens, device);
-  auto doff = to_device_i64(offs, device);
-  auto dsz = to_device_i64(sz, device).to(torch::kInt32);
-  auto ddt = to_device_i64(dt, device).to(torch::kInt32);
-  check_hip(anovos_label_counts_multi(
-                (const void *const *)dptr.data_ptr<int64_t>(),
-                label.data_ptr<uint8_t>(), dlen.data_ptr<int64_t>(),
-                doff.data_ptr<int64_t>(), dsz.data_ptr<int>(),
-                ddt.data_ptr<int>(), ncols, max_slots, nchunks,
-                (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
+  int nchunks = pick_chunks(b.maxn, b.ncols());
+  auto out = torch::zeros({off}, on(b.device, torch::kInt64));
+  auto dptr = upload(b.ptrs, b.device);
+  auto dlen = upload(b.lens, b.device);
+  auto doff = upload(offs, b.device);
+  auto dsz = upload(std::vector<int>(sizes.begin(), sizes.end()), b.device);
+  auto dkind = upload(kinds, b.device);
+  check_hip(anovos_label_counts_multi(ptr_table<const void>(dptr), label.data_ptr<uint8_t>(),
+                                      dlen.data_ptr<int64_t>(), doff.data_ptr<int64_t>(),
+                                      dsz.data_ptr<int>(), dkind.data_ptr<int>(), b.ncols(),
+                                      max_slots, nchunks, (uint64_t *)out.data_ptr<int64_t>(),
+                                      current_stream()),
             "anovos_label_counts_multi");
   return out;
 }
@@ -1042,64 +826,38 @@ torch::Tensor label_counts_multi(std::vector<torch::Tensor> cols,
 // materialization). Returns flat int64: per column [slots] totals then
 // [slots] events at offsets in the ORIGINAL column order.
 torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
-                                     std::vector<torch::Tensor> cutoffs,
-                                     torch::Tensor label,
+                                     std::vector<torch::Tensor> cutoffs, torch::Tensor label,
                                      std::vector<int64_t> sizes) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(cols.size() == cutoffs.size() && cols.size() == sizes.size(), "size mismatch");
-  TORCH_CHECK(label.is_contiguous() && label.scalar_type() == torch::kUInt8, "uint8 label required");
-  auto device = cols[0].device();
-  std::vector<int64_t> out_offs(cols.size());
+  ColumnBatch all = gather_columns(cols, "bucketize_label_counts", F32 | F64, /*equal_len=*/true);
+  check_count(cutoffs.size(), cols.size(), all.name, "cutoffs");
+  check_count(sizes.size(), cols.size(), all.name, "sizes");
+  check_dense_on_device(label, all, "label", torch::kUInt8, all.maxn);
+  auto device = all.device;
+  std::vector<int64_t> out_offs;
   int64_t total = 0;
-  for (size_t i = 0; i < cols.size(); ++i) {
-    TORCH_CHECK(sizes[i] >= 1 && sizes[i] <= 8192, "slot count out of LDS range");
-    TORCH_CHECK(cols[i].numel() == label.numel(), "column/label length mismatch");
-    out_offs[i] = total;
-    total += 2 * sizes[i];
+  for (int64_t s : sizes) {
+    TORCH_CHECK(s >= 1 && s <= LABEL_MAX_SLOTS, all.name, ": slot count out of LDS range");
+    out_offs.push_back(total);
+    total += 2 * s;
   }
-  auto out = torch::zeros({total}, torch::TensorOptions().dtype(torch::kInt64).device(device));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, offs, coffs;
-    std::vector<double> flat;
-    std::vector<int> clens;
-    std::vector<int64_t> sz;
-    int max_ncut = 1, max_slots = 1;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      TORCH_CHECK(cols[i].is_contiguous(), "contiguous columns required");
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      offs.push_back(out_offs[i]);
-      auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
-      coffs.push_back((int64_t)flat.size());
-      const double *cd = cc.data_ptr<double>();
-      flat.insert(flat.end(), cd, cd + cc.numel());
-      clens.push_back((int)cc.numel());
-      sz.push_back(sizes[i]);
-      max_ncut = std::max(max_ncut, (int)cc.numel());
-      max_slots = std::max(max_slots, (int)sizes[i]);
-    }
-    if (ptrs.empty()) continue;
-    if (flat.empty()) flat.push_back(0.0);  // from_blob on an empty vector's data() segfaults
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto doff = to_device_i64(offs, device);
-    auto dcoff = to_device_i64(coffs, device);
-    auto dflat = torch::from_blob(flat.data(), {(int64_t)std::max<size_t>(flat.size(), 1)},
-                                  torch::TensorOptions().dtype(torch::kFloat64)).clone().to(device);
-    auto dclen = torch::from_blob(clens.data(), {(int64_t)clens.size()},
-                                  torch::TensorOptions().dtype(torch::kInt32)).clone().to(device);
-    auto dsz = to_device_i64(sz, device).to(torch::kInt32);
+  auto out = torch::zeros({total}, on(device, torch::kInt64));
+  for (auto &b : split_by_dtype(all)) {
+    CutoffTable ct = cutoff_table(cutoffs, b.idx);
+    auto sz = pick(sizes, b.idx);
+    int max_slots = (int)std::max<int64_t>(1, *std::max_element(sz.begin(), sz.end()));
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto doff = upload(pick(out_offs, b.idx), device);
+    auto dcoff = upload(ct.offs, device);
+    auto dflat = upload(ct.flat, device);
+    auto dclen = upload(ct.lens, device);
+    auto dsz = upload(std::vector<int>(sz.begin(), sz.end()), device);
     check_hip(anovos_bucketize_label_counts(
-                  (const void *const *)dptr.data_ptr<int64_t>(),
-                  label.data_ptr<uint8_t>(), dlen.data_ptr<int64_t>(),
-                  dflat.data_ptr<double>(), dcoff.data_ptr<int64_t>(),
-                  dclen.data_ptr<int>(), doff.data_ptr<int64_t>(),
-                  dsz.data_ptr<int>(), ncols, max_ncut, max_slots, nchunks,
-                  pass, (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
+                  ptr_table<const void>(dptr), label.data_ptr<uint8_t>(), dlen.data_ptr<int64_t>(),
+                  dflat.data_ptr<double>(), dcoff.data_ptr<int64_t>(), dclen.data_ptr<int>(),
+                  doff.data_ptr<int64_t>(), dsz.data_ptr<int>(), b.ncols(), ct.max_ncut, max_slots,
+                  nchunks, b.dtype, (uint64_t *)out.data_ptr<int64_t>(), current_stream()),
               "anovos_bucketize_label_counts");
   }
   return out;
@@ -1110,104 +868,33 @@ torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
 // (counts [k,2] int64, outs list — empty when mode==0).
 std::tuple<torch::Tensor, std::vector<torch::Tensor>> outlier_clamp_columns(
     std::vector<torch::Tensor> cols, torch::Tensor lo, torch::Tensor hi, int64_t mode) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  auto device = cols[0].device();
-  auto lo_d = lo.to(torch::kFloat64).to(device).contiguous();
-  auto hi_d = hi.to(torch::kFloat64).to(device).contiguous();
-  auto counts = torch::zeros({(int64_t)cols.size(), 2},
-                             torch::TensorOptions().dtype(torch::kInt64).device(device));
-  std::vector<torch::Tensor> outs_all(cols.size());
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, optrs, idx;
-    std::vector<torch::Tensor> outs;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      if (dtype_code(cols[i]) != pass) continue;
-      TORCH_CHECK(cols[i].is_contiguous(), "columns must be contiguous");
-      ptrs.push_back((int64_t)cols[i].data_ptr());
-      lens.push_back(cols[i].numel());
-      idx.push_back((int64_t)i);
-      if (mode) {
-        auto o = torch::empty_like(cols[i]);
-        optrs.push_back((int64_t)o.data_ptr());
-        outs.push_back(o);
-      }
-    }
-    if (ptrs.empty()) continue;
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto didx = to_device_i64(idx, device);
+  ColumnBatch all = gather_columns(cols, "outlier_clamp_columns", F32 | F64);
+  auto device = all.device;
+  auto lo_d = device_f64(lo, cols.size(), all, "lo");
+  auto hi_d = device_f64(hi, cols.size(), all, "hi");
+  auto counts = torch::zeros({all.ncols(), 2}, on(device, torch::kInt64));
+  std::vector<torch::Tensor> outs;
+  if (mode)
+    for (auto &t : cols) outs.push_back(torch::empty_like(t));
+  for (auto &b : split_by_dtype(all)) {
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto didx = upload(b.idx, device);
     auto lo_sel = lo_d.index_select(0, didx);
     auto hi_sel = hi_d.index_select(0, didx);
-    auto sub = torch::zeros({ncols, 2}, torch::TensorOptions().dtype(torch::kInt64).device(device));
+    auto sub = torch::zeros({b.ncols(), 2}, on(device, torch::kInt64));
     torch::Tensor dout;
-    if (mode) dout = to_device_i64(optrs, device);
-    check_hip(anovos_outlier_clamp((const void *const *)dptr.data_ptr<int64_t>(),
-                                   dlen.data_ptr<int64_t>(), ncols,
-                                   lo_sel.data_ptr<double>(), hi_sel.data_ptr<double>(),
-                                   nchunks, (int)mode, pass,
-                                   mode ? (void *const *)dout.data_ptr<int64_t>() : nullptr,
+    if (mode) dout = upload(out_ptrs(outs, b), device);
+    check_hip(anovos_outlier_clamp(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
+                                   b.ncols(), lo_sel.data_ptr<double>(), hi_sel.data_ptr<double>(),
+                                   nchunks, (int)mode, b.dtype,
+                                   mode ? ptr_table<void>(dout) : nullptr,
                                    (uint64_t *)sub.data_ptr<int64_t>(), current_stream()),
               "anovos_outlier_clamp");
     counts.index_copy_(0, didx, sub);
-    for (size_t j = 0; j < idx.size(); ++j)
-      if (mode) outs_all[idx[j]] = outs[j];
   }
-  std::vector<torch::Tensor> outs_ret;
-  if (mode)
-    for (auto &o : outs_all) outs_ret.push_back(o);
-  return {counts, outs_ret};
-}
-
-
-// K1/K2+K4 fused: moments + HLL registers in one read.
-// Returns (moments [ncols,9] f64, regs [ncols, 1<<p] i32).
-std::tuple<torch::Tensor, torch::Tensor> moments_hll(std::vector<torch::Tensor> cols, int64_t p,
-                                                     std::vector<double> shifts) {
-  TORCH_CHECK(!cols.empty(), "no columns");
-  TORCH_CHECK(shifts.empty() || shifts.size() == cols.size(), "shifts must match cols");
-  auto device = cols[0].device();
-  int64_t m = 1LL << p;
-  auto mom = torch::zeros({(int64_t)cols.size(), 9},
-                          torch::TensorOptions().dtype(torch::kFloat64).device(device));
-  auto regs = torch::zeros({(int64_t)cols.size(), m},
-                           torch::TensorOptions().dtype(torch::kInt32).device(device));
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int64_t> ptrs, lens, idx;
-    std::vector<double> sh;
-    for (size_t i = 0; i < cols.size(); ++i) {
-      auto &t = cols[i];
-      TORCH_CHECK(t.is_contiguous() && t.device() == device, "columns must be contiguous, same device");
-      if (dtype_code(t) != pass) continue;
-      ptrs.push_back((int64_t)t.data_ptr());
-      lens.push_back(t.numel());
-      sh.push_back(shifts.empty() ? 0.0 : shifts[i]);
-      idx.push_back((int64_t)i);
-    }
-    if (ptrs.empty()) continue;
-    int ncols = (int)ptrs.size();
-    int64_t maxn = *std::max_element(lens.begin(), lens.end());
-    int nchunks = pick_chunks(maxn, ncols);
-    auto dptr = to_device_i64(ptrs, device);
-    auto dlen = to_device_i64(lens, device);
-    auto dsh = to_device_f64(sh, device);
-    auto partials = torch::empty({(int64_t)ncols * nchunks, 9},
-                                 torch::TensorOptions().dtype(torch::kFloat64).device(device));
-    auto mom_sub = torch::empty({ncols, 9}, torch::TensorOptions().dtype(torch::kFloat64).device(device));
-    auto reg_sub = torch::zeros({ncols, m}, torch::TensorOptions().dtype(torch::kInt32).device(device));
-    check_hip(anovos_moments_hll((const void *const *)dptr.data_ptr<int64_t>(),
-                                 dlen.data_ptr<int64_t>(), dsh.data_ptr<double>(),
-                                 ncols, (int)p, nchunks, pass,
-                                 partials.data_ptr<double>(), mom_sub.data_ptr<double>(),
-                                 reg_sub.data_ptr<int>(), current_stream()),
-              "anovos_moments_hll");
-    auto didx = to_device_i64(idx, device);
-    mom.index_copy_(0, didx, mom_sub);
-    regs.index_copy_(0, didx, reg_sub);
-  }
-  return {mom, regs};
+  return {counts, outs};
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

@@ -1,0 +1,129 @@
+// Launcher prototypes and host/device limits of the anovos_amd HIP kernels.
+//
+// Included by the bindings (anovos_bindings.hip) and by every file that
+// defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip):
+// the launchers have C linkage, so a definition whose parameter list
+// drifts from the prototype the bindings call through would link cleanly
+// and pass garbage; with the prototype in scope it fails to compile
+// ("conflicting types").
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+// ---- limits the host planning code and the kernels must agree on ----
+
+// K5 / K22: uint32 counters one block stages in LDS (64 KiB). A column of
+// code_counts(_multi) with more slots, or a pair table with more cells,
+// counts in global memory instead.
+constexpr int CODE_LDS_SLOTS = 16384;
+constexpr int PAIR_LDS_SLOTS = 16384;
+// K22 work item: anchor column + up to PAIR_PMAX partners, as
+// PAIR_ITEM_WORDS int64 words (layout in pair_counts.hip)
+constexpr int PAIR_PMAX = 8;
+constexpr int PAIR_ITEM_WORDS = 4 + 4 * PAIR_PMAX;
+// K3 grouped refinement histograms: sub-bins per bracket, brackets per
+// column and launch (RB_MAXB * RB_BINS uint32 counters in static LDS)
+constexpr int RB_BINS = 512;
+constexpr int RB_MAXB = 16;
+// K9: slots per column of the label-conditioned counts (2 * slots uint32
+// counters in LDS; slot numbers up to 8192 are exact in fp32)
+constexpr int LABEL_MAX_SLOTS = 8192;
+// K6 with counts: cutoffs per column (doubles + uint32 counters in LDS)
+constexpr int BKT_COUNTS_MAX_NCUT = 4096;
+
+// ---- launchers: return a hipError_t as int, 0 on success ----
+// dtype: 0 = float32 columns, 1 = float64 (K10 also 2 = int32 codes)
+
+extern "C" {
+int anovos_moments(const void *const *cols, const int64_t *lens,
+                   const double *shifts, int ncols, int nchunks, int dtype,
+                   double *partials, double *out, hipStream_t stream);
+int anovos_hist(const void *const *cols, const int64_t *lens, int ncols,
+                const double *lo, const double *hi, int nbins, int nchunks,
+                int dtype, uint64_t *out, hipStream_t stream);
+int anovos_bracket_hist(const void *const *cols, const int64_t *lens,
+                        const int64_t *colidx, int nbrackets, const double *lo,
+                        const double *hi, int nbins, int nchunks, int dtype,
+                        uint64_t *out, hipStream_t stream);
+int anovos_bucketize(const void *const *cols, const int64_t *lens, int ncols,
+                     const double *cutflat, const int64_t *cutoff_off,
+                     const int *cutoff_len, int max_ncut, int nchunks, int dtype,
+                     int32_t *const *outs, hipStream_t stream);
+int anovos_code_counts(const int32_t *codes, int64_t n, int size, int nchunks,
+                       uint64_t *out, hipStream_t stream);
+int anovos_hll(const void *x, int64_t n, int p, int nchunks, int dtype,
+               int32_t *regs, hipStream_t stream);
+int anovos_row_null(const void *const *cols, int ncols, int64_t n, int dtype,
+                    int32_t *out, hipStream_t stream);
+int anovos_hll_multi(const void *const *cols, const int64_t *lens, int ncols,
+                     int p, int nchunks, int dtype, int32_t *regs,
+                     hipStream_t stream);
+int anovos_axpb(const void *const *cols, const int64_t *lens, int ncols,
+                const double *a, const double *b, int nchunks, int dtype,
+                float *const *outs, hipStream_t stream);
+int anovos_fillnan(const void *const *cols, const int64_t *lens, int ncols,
+                   const double *fill, int nchunks, int dtype,
+                   void *const *outs, hipStream_t stream);
+int anovos_bracket_hist_grouped(const void *const *cols, const int64_t *lens,
+                                const int *bstart, int ncols, const double *lo,
+                                const double *hi, const double *p1lo,
+                                const double *p1scale, int p1bins, int nchunks,
+                                int dtype, uint64_t *out, hipStream_t stream);
+int anovos_bucketize_float(const void *const *cols, const int64_t *lens, int ncols,
+                           const double *cutflat, const int64_t *cutoff_off,
+                           const int *cutoff_len, int max_ncut, int nchunks, int dtype,
+                           float *const *outs, hipStream_t stream);
+int anovos_bucketize_float_counts(const void *const *cols, const int64_t *lens, int ncols,
+                                  const double *cutflat, const int64_t *cutoff_off,
+                                  const int *cutoff_len, int max_ncut, int nchunks, int dtype,
+                                  float *const *outs, uint64_t *counts, const int64_t *count_off,
+                                  hipStream_t stream);
+int anovos_lut_apply_f32(const int32_t *const *cols, const int64_t *lens, int ncols,
+                         const float *lutflat, const int64_t *lut_off, int nchunks,
+                         float *const *outs, hipStream_t stream);
+int anovos_lut_apply_i32(const int32_t *const *cols, const int64_t *lens, int ncols,
+                         const int32_t *lutflat, const int64_t *lut_off, int nchunks,
+                         int32_t *const *outs, hipStream_t stream);
+int anovos_fill_code(const int32_t *const *cols, const int64_t *lens, int ncols,
+                     const int32_t *fill, int nchunks, int32_t *const *outs,
+                     hipStream_t stream);
+int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
+                             const int64_t *offs, const int *sizes, int ncols,
+                             int lds_slots, int nchunks, uint64_t *out,
+                             hipStream_t stream);
+int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
+                         int ncols, const double *lo, const double *hi,
+                         int nchunks, int mode, int dtype, void *const *outs,
+                         uint64_t *counts, hipStream_t stream);
+int anovos_moments_hll(const void *const *cols, const int64_t *lens,
+                       const double *shifts, int ncols, int p, int nchunks,
+                       int dtype, double *partials, double *mom_out,
+                       int32_t *regs, hipStream_t stream);
+int anovos_bucketize_label_counts(const void *const *cols, const uint8_t *label,
+                                  const int64_t *lens, const double *cutflat,
+                                  const int64_t *cutoff_off, const int *cutoff_len,
+                                  const int64_t *offs, const int *sizes, int ncols,
+                                  int max_ncut, int max_slots, int nchunks,
+                                  int dtype, uint64_t *out, hipStream_t stream);
+int anovos_label_counts_multi(const void *const *cols, const uint8_t *label,
+                              const int64_t *lens, const int64_t *offs,
+                              const int *sizes, const int *dtypes, int ncols,
+                              int max_slots, int nchunks, uint64_t *out,
+                              hipStream_t stream);
+// corr_mfma.hip
+int anovos_centered_gram(const void *const *cols, int64_t n, int k,
+                         const float *means, const int *pair_i,
+                         const int *pair_j, int npairs, int row_chunks,
+                         float *partials, float *gram, hipStream_t stream);
+int anovos_centered_gram_sr(const void *const *cols, int64_t n, int k,
+                            const float *means, const int *pair_i,
+                            const int *pair_j, int npairs, int row_chunks,
+                            float *partials, float *gram, hipStream_t stream);
+int anovos_gram_sr_grid(int k);
+// pair_counts.hip
+int anovos_pair_code_counts(const int32_t *const *cols, const int64_t *items,
+                            int nitems, int64_t n, int64_t per, int nchunks,
+                            int lds_slots, uint64_t *out, hipStream_t stream);
+}

@@ -23,6 +23,8 @@
 #include <cstdint>
 #include <cmath>
 
+#include "anovos_kernels.h"
+
 #define THREADS 256
 #define DEV_INLINE __device__ __forceinline__
 
@@ -277,9 +279,6 @@ __global__ __launch_bounds__(THREADS) void bracket_hist_kernel(
 // O(1) per element instead of looping the bracket list; loads are
 // float4-vectorized. brackets are pre-sorted by column: col c owns
 // [bstart[c], bstart[c+1]).
-#define RB_BINS 512
-#define RB_MAXB 16
-
 template <typename T>
 __global__ __launch_bounds__(THREADS) void bracket_hist_grouped_kernel(
     const T *const *cols, const int64_t *lens, const int *bstart, int ncols,
@@ -719,7 +718,7 @@ __global__ __launch_bounds__(THREADS) void fill_code_kernel(
 __global__ __launch_bounds__(THREADS) void code_counts_kernel(
     const int32_t *codes, int64_t n, int size, int nchunks, uint64_t *out) {
   extern __shared__ uint32_t cnt[];
-  const bool use_lds = (size <= 16384);
+  const bool use_lds = (size <= CODE_LDS_SLOTS);
   if (use_lds) {
     for (int i = threadIdx.x; i < size; i += THREADS) cnt[i] = 0;
     __syncthreads();
@@ -1237,7 +1236,7 @@ int anovos_fill_code(const int32_t *const *cols, const int64_t *lens, int ncols,
 
 int anovos_code_counts(const int32_t *codes, int64_t n, int size, int nchunks,
                        uint64_t *out, hipStream_t stream) {
-  size_t lds = (size <= 16384) ? (size_t)size * 4 : 0;
+  size_t lds = (size <= CODE_LDS_SLOTS) ? (size_t)size * 4 : 0;
   hipLaunchKernelGGL(code_counts_kernel, dim3(nchunks), dim3(THREADS), lds, stream,
                      codes, n, size, nchunks, out);
   return (int)hipGetLastError();
@@ -1336,7 +1335,7 @@ __global__ __launch_bounds__(THREADS) void code_counts_multi_kernel(
   uint64_t *base = out + offs[col];
 
   extern __shared__ uint32_t cnt[];
-  const bool use_lds = (slots <= 16384);
+  const bool use_lds = (slots <= CODE_LDS_SLOTS);
   if (use_lds) {
     for (int i = threadIdx.x; i < slots; i += THREADS) cnt[i] = 0;
     __syncthreads();
@@ -1491,7 +1490,7 @@ int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
                              hipStream_t stream) {
   // lds_slots: the most slots (sizes[c] + 1) among the columns that stage
   // their counters in LDS (<= 16384 slots); 0 when none does
-  if (lds_slots < 0 || lds_slots > 16384) return (int)hipErrorInvalidValue;
+  if (lds_slots < 0 || lds_slots > CODE_LDS_SLOTS) return (int)hipErrorInvalidValue;
   size_t lds = (size_t)lds_slots * 4;
   hipLaunchKernelGGL(code_counts_multi_kernel, dim3(ncols * nchunks),
                      dim3(THREADS), lds, stream, cols, lens, offs, sizes,

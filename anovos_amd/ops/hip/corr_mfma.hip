@@ -28,6 +28,8 @@
 #include <cstdint>
 #include <cmath>
 
+#include "anovos_kernels.h"
+
 #define THREADS 256
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;

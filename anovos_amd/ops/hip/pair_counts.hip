@@ -24,12 +24,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "anovos_kernels.h"  // PAIR_PMAX, PAIR_LDS_SLOTS, PAIR_ITEM_WORDS
+
 #define THREADS 256
 #define DEV_INLINE __device__ __forceinline__
-
-#define PAIR_PMAX 8
-#define PAIR_LDS_SLOTS 16384
-#define PAIR_ITEM_WORDS (4 + 4 * PAIR_PMAX)
 
 typedef int nat_i4 __attribute__((ext_vector_type(4)));
 

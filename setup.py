@@ -10,7 +10,7 @@ setup(
     description="MI355X-native columnar feature-engineering engine (Anovos capabilities, no Spark)",
     packages=find_packages(include=["anovos_amd", "anovos_amd.*"]),
     package_data={
-        "anovos_amd.ops.hip": ["*.hip", "*.so", "build.py"],
+        "anovos_amd.ops.hip": ["*.hip", "*.h", "*.so", "build.py"],
         "anovos_amd.feature_recommender": ["data/*.csv", "data/README.md"],
         "anovos_amd.data_report": ["data/*.csv", "data/README.md"],
     },

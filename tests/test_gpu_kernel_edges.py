@@ -1062,3 +1062,149 @@ def test_bindings_reject_strided_views(ext):
             ext.lut_apply_f32(cols, [lut_f] * luts)
         with pytest.raises(RuntimeError, match="contiguous"):
             ext.lut_apply_i32(cols, [lut_i] * luts)
+
+
+def _column_list_calls(ext):
+    """binding name -> call(ts) for every binding that takes a column list;
+    all other arguments are valid for len(ts) columns of 32 rows. The
+    bool says whether the binding wants int32 code columns."""
+    f64 = torch.float64
+    cuts = torch.tensor([1.0, 2.0], dtype=f64)
+    b0 = torch.tensor([0], dtype=torch.int64)
+    lo1, hi1 = torch.tensor([0.0], dtype=f64), torch.tensor([10.0], dtype=f64)
+
+    def zeros(ts):
+        return torch.zeros(len(ts), dtype=f64)
+
+    def tens(ts):
+        return torch.full((len(ts),), 10.0, dtype=f64)
+
+    def label(ts):
+        return torch.zeros(32, dtype=torch.uint8, device=ts[0].device if ts else "cpu")
+
+    def out(ts):
+        return torch.zeros(32, dtype=torch.int32, device=ts[0].device if ts else "cpu")
+
+    floats = {
+        "column_moments": lambda ts: ext.column_moments(ts, []),
+        "moments_hll": lambda ts: ext.moments_hll(ts, 4),
+        "column_histograms": lambda ts: ext.column_histograms(ts, zeros(ts), tens(ts), 4),
+        "bracket_histograms": lambda ts: ext.bracket_histograms(ts, b0, lo1, hi1, 4),
+        "bracket_histograms_grouped": lambda ts: ext.bracket_histograms_grouped(
+            ts, b0, lo1, hi1, zeros(ts), tens(ts), 16),
+        "bucketize_columns": lambda ts: ext.bucketize_columns(ts, [cuts for _ in ts]),
+        "bucketize_columns_float": lambda ts: ext.bucketize_columns_float(ts, [cuts for _ in ts]),
+        "bucketize_columns_float_counts": lambda ts: ext.bucketize_columns_float_counts(ts, [cuts for _ in ts]),
+        "bucketize_label_counts": lambda ts: ext.bucketize_label_counts(
+            ts, [cuts for _ in ts], label(ts), [4 for _ in ts]),
+        "hll_registers_multi": lambda ts: ext.hll_registers_multi(ts, 4),
+        "scale_columns": lambda ts: ext.scale_columns(ts, zeros(ts), tens(ts)),
+        "fill_nan_columns": lambda ts: ext.fill_nan_columns(ts, zeros(ts)),
+        "outlier_clamp_columns": lambda ts: ext.outlier_clamp_columns(ts, zeros(ts), tens(ts), 1),
+        "centered_gram_bf16": lambda ts: ext.centered_gram_bf16(ts, torch.zeros(len(ts))),
+        "row_null_counts_num": lambda ts: ext.row_null_counts_num(ts, out(ts)),
+    }
+    codes = {
+        "fill_code_columns": lambda ts: ext.fill_code_columns(ts, [7 for _ in ts]),
+        "lut_apply_f32": lambda ts: ext.lut_apply_f32(ts, [torch.zeros(3) for _ in ts]),
+        "lut_apply_i32": lambda ts: ext.lut_apply_i32(ts, [torch.zeros(3, dtype=torch.int32) for _ in ts]),
+        "code_counts_multi": lambda ts: ext.code_counts_multi(ts, [3 for _ in ts]),
+        "pair_code_counts": lambda ts: ext.pair_code_counts(ts, [3 for _ in ts], [0], [len(ts) - 1]),
+        "label_counts_multi": lambda ts: ext.label_counts_multi(ts, label(ts), [4 for _ in ts]),
+    }
+    return [(n, c, False) for n, c in floats.items()] + [(n, c, True) for n, c in codes.items()]
+
+
+def test_bindings_reject_host_and_empty_lists():
+    """No binding lets an empty column list or host tensors past its first
+    check: the refusal comes before any device call, so this runs without
+    a GPU (with one, a missing check would hand host pointers to a kernel)."""
+    from anovos_amd.ops import backend
+
+    ext = backend.hip_ext()
+    if ext is None:
+        pytest.skip("HIP extension not built")
+    host_f = [torch.arange(32, dtype=torch.float32), torch.ones(32, dtype=torch.float32)]
+    host_c = [torch.zeros(32, dtype=torch.int32), torch.ones(32, dtype=torch.int32)]
+    calls = _column_list_calls(ext)
+    assert len(calls) == 21
+    for name, call, wants_codes in calls:
+        with pytest.raises(RuntimeError, match=name + ": no columns"):
+            call([])
+        for ts in ([host_c[0]], host_c) if wants_codes else ([host_f[0]], host_f):
+            with pytest.raises(RuntimeError, match=name + ": device columns required"):
+                call(ts)
+    # the two bindings that take one column
+    with pytest.raises(RuntimeError, match="hll_registers: device columns required"):
+        ext.hll_registers(host_f[0], 4)
+    with pytest.raises(RuntimeError, match="code_counts: device columns required"):
+        ext.code_counts(host_c[0], 3)
+
+
+@requires_gpu
+@pytest.mark.gpu
+def test_bindings_reject_short_parameter_arrays(ext):
+    """Per-column and per-bracket arrays one entry short, a column index
+    past the list, and a host `label` / `out` next to device columns are
+    refused; the same call with the argument right succeeds."""
+    f64 = torch.float64
+    ts = [torch.arange(32, dtype=torch.float32, device=DEV), torch.ones(32, dtype=torch.float32, device=DEV)]
+    cs = [torch.zeros(32, dtype=torch.int32, device=DEV), torch.ones(32, dtype=torch.int32, device=DEV)]
+    for name, call, wants_codes in _column_list_calls(ext):
+        call(cs if wants_codes else ts)  # every call of the table is valid as it stands
+
+    def vec(k, v=0.0):
+        return torch.full((k,), v, dtype=f64)
+
+    cuts = torch.tensor([1.0, 2.0], dtype=f64)
+    lut_f, lut_i = torch.zeros(3), torch.zeros(3, dtype=torch.int32)
+    bidx = torch.tensor([0, 1], dtype=torch.int64)
+    label = torch.zeros(32, dtype=torch.uint8, device=DEV)
+    out = torch.zeros(32, dtype=torch.int32, device=DEV)
+    # name -> call(k): k entries in the array under test; 2 is right
+    short = {
+        "scale a": lambda k: ext.scale_columns(ts, vec(k), vec(2, 10.0)),
+        "scale b": lambda k: ext.scale_columns(ts, vec(2), vec(k, 10.0)),
+        "fill_nan fill": lambda k: ext.fill_nan_columns(ts, vec(k)),
+        "hist lo": lambda k: ext.column_histograms(ts, vec(k), vec(2, 10.0), 4),
+        "hist hi": lambda k: ext.column_histograms(ts, vec(2), vec(k, 10.0), 4),
+        "outlier lo": lambda k: ext.outlier_clamp_columns(ts, vec(k), vec(2, 10.0), 1),
+        "outlier hi": lambda k: ext.outlier_clamp_columns(ts, vec(2), vec(k, 10.0), 0),
+        "bracket lo": lambda k: ext.bracket_histograms(ts, bidx, vec(k), vec(2, 10.0), 4),
+        "bracket hi": lambda k: ext.bracket_histograms(ts, bidx, vec(2), vec(k, 10.0), 4),
+        "grouped lo": lambda k: ext.bracket_histograms_grouped(ts, bidx, vec(k), vec(2, 10.0), vec(2), vec(2, 1.6), 16),
+        "grouped hi": lambda k: ext.bracket_histograms_grouped(ts, bidx, vec(2), vec(k, 10.0), vec(2), vec(2, 1.6), 16),
+        "grouped p1lo": lambda k: ext.bracket_histograms_grouped(ts, bidx, vec(2), vec(2, 10.0), vec(k), vec(2, 1.6), 16),
+        "grouped p1scale": lambda k: ext.bracket_histograms_grouped(ts, bidx, vec(2), vec(2, 10.0), vec(2), vec(k, 1.6), 16),
+        "luts f32": lambda k: ext.lut_apply_f32(cs, [lut_f] * k),
+        "luts i32": lambda k: ext.lut_apply_i32(cs, [lut_i] * k),
+        "cutoffs int": lambda k: ext.bucketize_columns(ts, [cuts] * k),
+        "cutoffs float": lambda k: ext.bucketize_columns_float(ts, [cuts] * k),
+        "cutoffs counts": lambda k: ext.bucketize_columns_float_counts(ts, [cuts] * k),
+        "cutoffs label": lambda k: ext.bucketize_label_counts(ts, [cuts] * k, label, [4, 4]),
+        "sizes bucketize_label": lambda k: ext.bucketize_label_counts(ts, [cuts] * 2, label, [4] * k),
+        "sizes label_counts": lambda k: ext.label_counts_multi(cs, label, [4] * k),
+        "sizes code_counts": lambda k: ext.code_counts_multi(cs, [3] * k),
+        "sizes pair_counts": lambda k: ext.pair_code_counts(cs, [3] * k, [0], [1]),
+        "fills": lambda k: ext.fill_code_columns(cs, [7] * k),
+        "gram means": lambda k: ext.centered_gram_bf16(ts, torch.zeros(k)),
+    }
+    for name, call in short.items():
+        call(2)
+        with pytest.raises(RuntimeError, match="has 1 entries, expected 2"):
+            call(1)
+    # a bracket that names a column past the list
+    ext.bracket_histograms(ts, torch.tensor([1]), vec(1), vec(1, 10.0), 4)
+    with pytest.raises(RuntimeError, match="colidx"):
+        ext.bracket_histograms(ts, torch.tensor([2]), vec(1), vec(1, 10.0), 4)
+    # host label / out next to device columns
+    ext.label_counts_multi(cs, label, [4, 4])
+    with pytest.raises(RuntimeError, match="label"):
+        ext.label_counts_multi(cs, label.cpu(), [4, 4])
+    ext.bucketize_label_counts(ts, [cuts] * 2, label, [4, 4])
+    with pytest.raises(RuntimeError, match="label"):
+        ext.bucketize_label_counts(ts, [cuts] * 2, label.cpu(), [4, 4])
+    ext.row_null_counts_num(ts, out)
+    with pytest.raises(RuntimeError, match="out"):
+        ext.row_null_counts_num(ts, out.cpu())
+    assert out.cpu().tolist() == [0] * 32  # no NaN in ts, nothing added
