@@ -6,6 +6,9 @@ data_analyzer/association_evaluator.py (586 LoC).
   VarClusHi (association_eval_varclus.py),
 - IV_calculation (:253): per-bin label histograms (K9) + WOE/IV sums,
 - IG_calculation (:427): entropy before/after split.
+
+Beyond the reference: categorical_association_matrix (pair-count kernel,
+K22) and numerical_categorical_association (grouped-moments kernel, K23).
 """
 
 from __future__ import annotations
@@ -538,6 +541,114 @@ def categorical_association_matrix(
     odf["attribute"] = odf.index
     sorted_cols = sorted(cols)
     odf = odf[["attribute"] + sorted_cols].sort_values("attribute").reset_index(drop=True)
+    if print_impact:
+        print(odf.to_string(index=False))
+    return odf
+
+
+def _anova_stats(mom: np.ndarray):
+    """(eta_squared, anova_f) of one pair from its per-group moments
+    [(n, mean, M2)] whose LAST row is the null slot — fp64 numpy
+    throughout. The null slot goes first (pairwise-complete rows), then
+    groups without a row; k groups and N rows remain. SSW is the sum of the
+    groups' M2, never SST - SSB, so eta near 1 does not cancel. Undefined
+    entries are NaN."""
+    nan = float("nan")
+    m = np.asarray(mom, dtype=np.float64)[:-1]
+    m = m[m[:, 0] > 0]
+    k = m.shape[0]
+    if k < 2:
+        return nan, nan
+    n, mean, m2 = m[:, 0], m[:, 1], m[:, 2]
+    if not (np.isfinite(mean).all() and np.isfinite(m2).all()):
+        return nan, nan  # a non-finite value among the rows used
+    big_n = float(n.sum())
+    # group means about the first one: equal means give SSB = 0 exactly,
+    # whatever the rounding of the grand mean
+    delta = mean - mean[0]
+    mu = float((n * delta).sum()) / big_n
+    ssw = float(m2.sum())
+    ssb = float((n * (delta - mu) ** 2).sum())
+    sst = ssb + ssw
+    eta2 = min(max(ssb / sst, 0.0), 1.0) if sst > 0 else nan
+    f = nan
+    if big_n > k:
+        if ssw > 0:
+            f = (ssb / (k - 1)) / (ssw / (big_n - k))
+        elif ssb > 0:
+            f = float("inf")
+    return eta2, f
+
+
+@traced
+def numerical_categorical_association(
+    ctx,
+    idf,
+    list_of_cols="all",
+    drop_cols=[],
+    method_type="correlation_ratio",
+    max_categories=1000,
+    print_impact=False,
+):
+    """[attribute, <numerical cols...>], one row per categorical attribute —
+    how much of a numerical attribute a categorical one explains, beyond
+    the reference, which has no measure for this kind of pair.
+
+    method_type: "eta_squared" (SSB / SST, [0, 1]), "correlation_ratio"
+    (its square root) or "anova_f" (the one-way ANOVA F statistic,
+    (SSB / (k - 1)) / (SSW / (N - k)); +inf where the groups differ and no
+    group varies). Every pair uses its pairwise-complete rows (non-null
+    category, non-NaN value) and drops empty groups; undefined entries
+    (fewer than two groups, a constant numerical attribute for the eta
+    methods, N <= k for anova_f, a non-finite value) are NaN. Categorical
+    columns with more than max_categories dictionary entries are left out
+    with a warning. One pass of the grouped-moments kernel (K23) yields
+    (n, mean, M2) per group for all pairs; the statistics are fp64 numpy on
+    the host, not rounded."""
+    from anovos_amd.ops.grouped import grouped_moments
+    from anovos_amd.ops.groupby import align_dictionaries
+
+    if method_type not in ("correlation_ratio", "eta_squared", "anova_f"):
+        raise TypeError("Invalid input for method_type")
+    num_cols, cat_cols, _ = attributeType_segregation(idf)
+    if list_of_cols == "all":
+        list_of_cols = num_cols + cat_cols
+    if isinstance(list_of_cols, str):
+        list_of_cols = [x.strip() for x in list_of_cols.split("|")]
+    if isinstance(drop_cols, str):
+        drop_cols = [x.strip() for x in drop_cols.split("|")]
+    cols = [e for e in dict.fromkeys(list_of_cols) if e not in list(drop_cols)]
+    if any(x not in num_cols + cat_cols for x in cols) or len(cols) == 0:
+        raise TypeError("Invalid input for Column(s)")
+
+    my_cat = [c for c in cols if c in cat_cols]
+    my_num = [c for c in cols if c in num_cols]
+    # dictionary sizes decide which columns stay: make them rank-identical first
+    align_dictionaries(idf, my_cat)
+    too_wide = [c for c in my_cat if len(idf.col(c).dictionary or []) > max_categories]
+    if too_wide:
+        warnings.warn(
+            "numerical_categorical_association: more than " + str(max_categories)
+            + " categories, column(s) left out: " + ", ".join(too_wide)
+        )
+        my_cat = [c for c in my_cat if c not in too_wide]
+    if len(my_cat) == 0 or len(my_num) == 0:
+        raise TypeError("Invalid input for Column(s)")
+
+    my_cat, my_num = sorted(my_cat), sorted(my_num)
+    moments = grouped_moments(idf, my_cat, my_num)
+    mat = np.full((len(my_cat), len(my_num)), np.nan, dtype=np.float64)
+    for a, c in enumerate(my_cat):
+        for b, v in enumerate(my_num):
+            eta2, f = _anova_stats(moments[(c, v)])
+            if method_type == "anova_f":
+                mat[a, b] = f
+            elif method_type == "eta_squared":
+                mat[a, b] = eta2
+            else:
+                mat[a, b] = math.sqrt(eta2) if eta2 == eta2 else np.nan
+    odf = pd.DataFrame(mat, columns=my_num)
+    odf.insert(0, "attribute", my_cat)
     if print_impact:
         print(odf.to_string(index=False))
     return odf

@@ -1,5 +1,5 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
-// corr_mfma.hip, pair_counts.hip). Compiled by torch.utils.cpp_extension
+// corr_mfma.hip, pair_counts.hip, grouped_moments.hip). Compiled by torch.utils.cpp_extension
 // with hipcc for gfx950; streams come from the caller's current torch HIP
 // stream so kernels compose with the engine's side-stream overlap
 // (core/dist.py SideStream).
@@ -786,6 +786,158 @@ std::vector<int64_t> pair_code_counts_plan(std::vector<int64_t> sizes, std::vect
   return {(int64_t)plan.nitems, plan.col_reads, (int64_t)plan.lds_slots};
 }
 
+// K23: (n, s1, s2) of value columns per slot of a code column. The kernel
+// (grouped_moments.hip) takes work items "code column + slot window + up
+// to GRP_PMAX value columns".
+namespace {
+
+struct GroupPlan {
+  std::vector<int64_t> items;  // GRP_ITEM_WORDS words per item
+  int nitems = 0;
+  int cells = 0;               // most accumulator cells (w * P) of any item
+  int64_t col_reads = 0;       // column streams per row chunk: sum(1 + P)
+};
+
+// Output offset of every pair's [size + 1][3] block, in pair order; the
+// last entry is the total. Range-checks sizes and pair indices.
+std::vector<int64_t> group_offsets(const std::vector<int64_t> &sizes, int64_t nvals,
+                                   const std::vector<int64_t> &pair_c,
+                                   const std::vector<int64_t> &pair_v) {
+  const int64_t ncodes = (int64_t)sizes.size();
+  TORCH_CHECK(pair_c.size() == pair_v.size(), "pair_c/pair_v length mismatch");
+  for (auto s : sizes) TORCH_CHECK(s >= 0 && s < INT32_MAX, "dictionary size out of range");
+  std::vector<int64_t> offs{0};
+  for (size_t q = 0; q < pair_c.size(); ++q) {
+    TORCH_CHECK(pair_c[q] >= 0 && pair_c[q] < ncodes && pair_v[q] >= 0 && pair_v[q] < nvals,
+                "pair index out of range");
+    offs.push_back(offs.back() + 3 * (sizes[pair_c[q]] + 1));
+  }
+  return offs;
+}
+
+// Items of the pairs whose value column is in `vpos` (value column ->
+// position in the launch's value table, -1: another dtype's launch). Pairs
+// are grouped by code column in order of first appearance. A dictionary
+// whose slots fit GRP_CELLS packs min(GRP_PMAX, GRP_CELLS / slots) value
+// columns per item in pair order; a larger one takes one item per window
+// of GRP_CELLS slots and pair.
+GroupPlan plan_group_items(const std::vector<int64_t> &sizes, const std::vector<int64_t> &vpos,
+                           const std::vector<int64_t> &pair_c, const std::vector<int64_t> &pair_v,
+                           const std::vector<int64_t> &offs) {
+  GroupPlan plan;
+  std::vector<std::vector<int64_t>> by_code(sizes.size());
+  std::vector<int64_t> order;
+  for (size_t q = 0; q < pair_c.size(); ++q) {
+    if (vpos[pair_v[q]] < 0) continue;
+    if (by_code[pair_c[q]].empty()) order.push_back(pair_c[q]);
+    by_code[pair_c[q]].push_back((int64_t)q);
+  }
+  auto open_item = [&](int64_t c, int64_t g0, int64_t w) {
+    plan.items.resize(plan.items.size() + GRP_ITEM_WORDS, 0);
+    int64_t *it = plan.items.data() + (int64_t)plan.nitems * GRP_ITEM_WORDS;
+    it[0] = c;
+    it[1] = sizes[c];
+    it[3] = g0;
+    it[4] = w;
+    plan.nitems += 1;
+    plan.col_reads += 1;
+  };
+  auto add_value = [&](int64_t q) {
+    int64_t *it = plan.items.data() + (int64_t)(plan.nitems - 1) * GRP_ITEM_WORDS;
+    it[5 + 2 * it[2]] = vpos[pair_v[q]];
+    it[6 + 2 * it[2]] = offs[q];
+    it[2] += 1;
+    plan.col_reads += 1;
+    plan.cells = std::max(plan.cells, (int)(it[2] * it[4]));
+  };
+  for (int64_t c : order) {
+    const int64_t slots = sizes[c] + 1;
+    if (slots <= GRP_CELLS) {
+      const int64_t pmax = std::min<int64_t>(GRP_PMAX, GRP_CELLS / slots);
+      int64_t np = pmax;
+      for (int64_t q : by_code[c]) {
+        if (np == pmax) {
+          open_item(c, 0, slots);
+          np = 0;
+        }
+        add_value(q);
+        np += 1;
+      }
+    } else {
+      for (int64_t q : by_code[c])
+        for (int64_t g0 = 0; g0 < slots; g0 += GRP_CELLS) {
+          open_item(c, g0, std::min<int64_t>(GRP_CELLS, slots - g0));
+          add_value(q);
+        }
+    }
+    TORCH_CHECK((int64_t)plan.items.size() / GRP_ITEM_WORDS < (int64_t)INT32_MAX, "too many work items");
+  }
+  return plan;
+}
+
+}  // namespace
+
+// Flat fp64 of the slot-major blocks [sizes[c] + 1][3] = (n, s1, s2) of the
+// pairs (pair_c[q], pair_v[q]), in pair order: rows per slot, sum d and
+// sum d^2 with d = (double)x - shifts[v] over the rows whose value is not
+// NaN; the null slot (any code outside [0, size)) is each block's last row.
+torch::Tensor grouped_moments(std::vector<torch::Tensor> codes, std::vector<int64_t> sizes,
+                              std::vector<torch::Tensor> values, std::vector<double> shifts,
+                              std::vector<int64_t> pair_c, std::vector<int64_t> pair_v) {
+  ColumnBatch cb = gather_columns(codes, "grouped_moments", I32, /*equal_len=*/true);
+  ColumnBatch vb = gather_columns(values, "grouped_moments", F32 | F64, /*equal_len=*/true);
+  TORCH_CHECK(vb.device == cb.device, cb.name, ": columns must be on the same device");
+  TORCH_CHECK(vb.maxn == cb.maxn, cb.name, ": all columns must have equal length");
+  for (auto &t : codes) TORCH_CHECK(t.dim() == 1, cb.name, ": columns must be 1-D");
+  for (auto &t : values) TORCH_CHECK(t.dim() == 1, cb.name, ": columns must be 1-D");
+  check_count(sizes.size(), codes.size(), cb.name, "sizes");
+  check_count(shifts.size(), values.size(), cb.name, "shifts");
+  const int64_t n = cb.maxn;
+  auto offs = group_offsets(sizes, vb.ncols(), pair_c, pair_v);
+  auto device = cb.device;
+  auto out = torch::zeros({offs.back()}, on(device, torch::kFloat64));
+  if (n == 0 || pair_c.empty()) return out;
+  auto dcodes = upload(cb.ptrs, device);
+  for (auto &b : split_by_dtype(vb)) {
+    std::vector<int64_t> vpos(vb.ncols(), -1);
+    for (int j = 0; j < b.ncols(); ++j) vpos[b.idx[j]] = j;
+    GroupPlan plan = plan_group_items(sizes, vpos, pair_c, pair_v, offs);
+    if (plan.nitems == 0) continue;
+    int nchunks = pick_chunks(n, plan.nitems);
+    // chunk length a multiple of 4 rows: every chunk then starts at the same
+    // offset inside a 16-byte line as the column itself
+    const int64_t per = (((n + nchunks - 1) / nchunks) + 3) / 4 * 4;
+    // a thread's row counter holds at most its share of one block's rows
+    TORCH_CHECK(per / GRP_THREADS < (int64_t)UINT32_MAX, "rows per thread exceed the 32-bit LDS counters");
+    TORCH_CHECK((int64_t)plan.nitems * nchunks <= (int64_t)INT32_MAX, "grid too large");
+    auto dvals = upload(b.ptrs, device);
+    auto dsh = upload(pick(shifts, b.idx), device);
+    auto ditems = upload(plan.items, device);
+    auto partials = torch::empty({(int64_t)plan.nitems * nchunks * GRP_CELLS * 3}, on(device, torch::kFloat64));
+    check_hip(anovos_grouped_moments(ptr_table<const int32_t>(dcodes), ptr_table<const void>(dvals),
+                                     dsh.data_ptr<double>(), ditems.data_ptr<int64_t>(), plan.nitems,
+                                     n, per, nchunks, plan.cells, b.dtype,
+                                     partials.data_ptr<double>(), out.data_ptr<double>(),
+                                     current_stream()),
+              "anovos_grouped_moments");
+  }
+  return out;
+}
+
+// [work items, column streams per row chunk, accumulator cells of the
+// launch] for a pair list whose value columns share one dtype — what the
+// benchmark needs to count the bytes read.
+std::vector<int64_t> grouped_moments_plan(std::vector<int64_t> sizes, std::vector<int64_t> pair_c,
+                                          std::vector<int64_t> pair_v) {
+  int64_t nvals = 0;
+  for (int64_t v : pair_v) nvals = std::max(nvals, v + 1);
+  auto offs = group_offsets(sizes, nvals, pair_c, pair_v);
+  std::vector<int64_t> vpos(nvals);
+  for (int64_t j = 0; j < nvals; ++j) vpos[j] = j;
+  GroupPlan plan = plan_group_items(sizes, vpos, pair_c, pair_v, offs);
+  return {(int64_t)plan.nitems, plan.col_reads, (int64_t)plan.cells};
+}
+
 // K9 fused: label-conditioned histograms, ALL columns in one launch.
 // Per column at out[off]: [slots] totals then [slots] event counts.
 // Column dtype drives the slot mapping (f32 binned vs int32 codes).
@@ -902,6 +1054,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pair_code_counts", &pair_code_counts, "contingency tables of code-column pairs (K22)");
   m.def("pair_code_counts_plan", &pair_code_counts_plan,
         "[items, column streams, LDS counters] of a K22 pair list");
+  m.def("grouped_moments", &grouped_moments, "(n, s1, s2) of value columns per code slot (K23)");
+  m.def("grouped_moments_plan", &grouped_moments_plan,
+        "[items, column streams, accumulator cells] of a K23 pair list");
+  m.attr("GRP_CELLS") = GRP_CELLS;
   m.def("outlier_clamp_columns", &outlier_clamp_columns, "fused outlier count/clamp (K10/K11)");
   m.def("label_counts_multi", &label_counts_multi, "fused multi-column label-conditioned histograms (K9)");
   m.def("bucketize_label_counts", &bucketize_label_counts, "fused bucketize + label counts, no binned materialization (K6+K9)");

@@ -1,7 +1,8 @@
 // Launcher prototypes and host/device limits of the anovos_amd HIP kernels.
 //
 // Included by the bindings (anovos_bindings.hip) and by every file that
-// defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip):
+// defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
+// grouped_moments.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -23,6 +24,17 @@ constexpr int PAIR_LDS_SLOTS = 16384;
 // PAIR_ITEM_WORDS int64 words (layout in pair_counts.hip)
 constexpr int PAIR_PMAX = 8;
 constexpr int PAIR_ITEM_WORDS = 4 + 4 * PAIR_PMAX;
+// K23 work item: one code column, a window of w slots and P value columns
+// with w * P <= GRP_CELLS accumulator cells, P <= GRP_PMAX, as
+// GRP_ITEM_WORDS int64 words (layout in grouped_moments.hip). Every thread
+// of a block owns GRP_CELL_BYTES of LDS per cell (fp64 s1, fp64 s2, uint32
+// row count): GRP_CELLS * GRP_THREADS * GRP_CELL_BYTES = 80 KiB, two
+// blocks per CU.
+constexpr int GRP_CELLS = 16;
+constexpr int GRP_PMAX = 8;
+constexpr int GRP_THREADS = 256;
+constexpr int GRP_CELL_BYTES = 20;
+constexpr int GRP_ITEM_WORDS = 5 + 2 * GRP_PMAX;
 // K3 grouped refinement histograms: sub-bins per bracket, brackets per
 // column and launch (RB_MAXB * RB_BINS uint32 counters in static LDS)
 constexpr int RB_BINS = 512;
@@ -126,4 +138,9 @@ int anovos_gram_sr_grid(int k);
 int anovos_pair_code_counts(const int32_t *const *cols, const int64_t *items,
                             int nitems, int64_t n, int64_t per, int nchunks,
                             int lds_slots, uint64_t *out, hipStream_t stream);
+// grouped_moments.hip
+int anovos_grouped_moments(const int32_t *const *codes, const void *const *vals,
+                           const double *shifts, const int64_t *items, int nitems,
+                           int64_t n, int64_t per, int nchunks, int cells, int dtype,
+                           double *partials, double *out, hipStream_t stream);
 }
