@@ -112,35 +112,38 @@ def nullRows_detection(ctx, idf, list_of_cols="all", drop_cols=[], treatment=Fal
         raise TypeError("Invalid input for Treatment Threshold Value")
 
     counts = rowops.row_null_counts(idf, cols)  # [local_rows] int32
-    if treatment_threshold == 1:
-        flagged = counts == len(cols)
-    else:
-        flagged = counts > (len(cols) * treatment_threshold)
+
+    def flag(t):
+        # one rule for the rows (treatment) and for the histogram buckets
+        if treatment_threshold == 1:
+            return t == len(cols)
+        return t > (len(cols) * treatment_threshold)
 
     total = idf.count()
-    # (null_count, flagged) key histogram: LDS-staged code_counts on GPU
-    # (a torch scatter_add here costs ~1.8 s of fp64 atomic contention on
-    # 10M rows — measured; bincount/code_counts is ~1000x cheaper)
-    key = counts.to(torch.int32) * 2 + flagged.to(torch.int32)
-    size = (len(cols) + 1) * 2
+    # null-count histogram: LDS-staged code_counts on GPU (a torch
+    # scatter_add here costs ~1.8 s of fp64 atomic contention on 10M rows —
+    # measured; bincount/code_counts is ~1000x cheaper). `flagged` is a
+    # function of the count alone, so the buckets are split by it on the
+    # host and no per-row key is built.
+    size = len(cols) + 1
     from anovos_amd.ops import backend as _backend
 
-    if key.is_cuda and _backend.use_hip(key):
-        hist = _backend.hip_ext().code_counts(key.contiguous(), size).to(torch.float64)
+    if counts.is_cuda and _backend.use_hip(counts):
+        hist = _backend.hip_ext().code_counts(counts.contiguous(), size).to(torch.float64)
     else:
-        hist = torch.bincount(key.to(torch.long), minlength=size).to(torch.float64)
+        hist = torch.bincount(counts.to(torch.long), minlength=size).to(torch.float64)
     dist.all_reduce_(hist, "sum")
     hist_l = hist.cpu().numpy().tolist()
+    bucket_flag = flag(torch.arange(size, dtype=torch.int32)).tolist()
     rows = []
-    for nc in range(len(cols) + 1):
-        for fl in (0, 1):
-            c = hist_l[nc * 2 + fl]
-            if c > 0:
-                rows.append([nc, int(c), round(c / total, 4), fl])
+    for nc in range(size):
+        c = hist_l[nc]
+        if c > 0:
+            rows.append([nc, int(c), round(c / total, 4), int(bucket_flag[nc])])
     odf_print = pd.DataFrame(rows, columns=["null_cols_count", "row_count", "row_pct", "flagged"])
 
     if treatment:
-        odf = idf.filter_rows(~flagged)
+        odf = idf.filter_rows(~flag(counts))
         odf_print = odf_print.rename(columns={"flagged": "treated"})
     else:
         odf = idf

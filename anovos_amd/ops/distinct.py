@@ -115,11 +115,18 @@ def approx_distinct(idf, cols: List[str]) -> Dict[str, int]:
         if len(cold) >= max(2, len(cols) // 2):
             # fused K1/K2+K4: the same read fills the moment cache every
             # later analyzer section will hit (ops/hip moments_hll)
+            from anovos_amd.ops import rowops
             from anovos_amd.ops import stats as stats_ops
 
             tensors = [idf.col(c).data.contiguous() for c in cols]
             shifts = stats_ops.compute_column_shifts(tensors)
-            mom_local, flat = ext.moments_hll(tensors, HLL_P, shifts)
+            if rowops.null_masks_enabled():
+                # ... and leaves each f32 column's null lane mask for the
+                # row-null scan (ops/rowops.py), rank-local
+                mom_local, flat, masks, parts = ext.moments_hll(tensors, HLL_P, shifts, null_masks=True)
+                rowops.store_null_masks(idf, cols, masks, parts)
+            else:
+                mom_local, flat = ext.moments_hll(tensors, HLL_P, shifts)
             glob = stats_ops.merge_moments_global(mom_local).numpy().tolist()
             for i, c in enumerate(cols):
                 idf.col(c).cache.setdefault("moments", stats_ops.MomentStats(glob[i], shift=shifts[i]))

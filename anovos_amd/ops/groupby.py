@@ -87,9 +87,18 @@ def cat_value_counts(idf, cols: List[str]) -> Dict[str, torch.Tensor]:
     if gpu_cols:
         # one fused launch for every uncached categorical column (K5);
         # the per-column null slot feeds the null-count cache for free
+        from anovos_amd.ops import rowops
+
         ext = backend.hip_ext()
         sizes = [len(idf.col(c).dictionary or []) for c in gpu_cols]
-        flat_multi = ext.code_counts_multi([idf.col(c).data.contiguous() for c in gpu_cols], sizes)
+        codes_multi = [idf.col(c).data.contiguous() for c in gpu_cols]
+        if rowops.null_masks_enabled():
+            # the same read leaves each LDS-counted column's null lane mask
+            # for the row-null scan (ops/rowops.py), rank-local
+            flat_multi, masks, parts = ext.code_counts_multi(codes_multi, sizes, null_masks=True)
+            rowops.store_null_masks(idf, gpu_cols, masks, parts)
+        else:
+            flat_multi = ext.code_counts_multi(codes_multi, sizes)
         gpu_cnt = {}
         off = 0
         for c, size in zip(gpu_cols, sizes):

@@ -185,10 +185,31 @@ CutoffTable cutoff_table(const std::vector<torch::Tensor> &cutoffs, const std::v
   return ct;
 }
 
-// K1/K2 (p < 0) and K1/K2+K4 fused (p >= 0: HLL registers from the same read).
+// Null lane masks of one binding call, by original column position: an
+// int64 tensor of nchunks * null_mask_chunk_words(per) words and the
+// partition {n, nchunks, per} it was made with; an undefined tensor and an
+// empty partition for a column whose launch emits none.
+struct NullMasks {
+  std::vector<torch::Tensor> masks;
+  std::vector<std::vector<int64_t>> parts;
+  explicit NullMasks(size_t ncols) : masks(ncols), parts(ncols) {}
+
+  // allocates column i's mask (left unwritten: the kernel writes every
+  // word the reader looks at) and returns its address
+  int64_t add(int64_t i, int64_t n, int nchunks, const torch::Device &dev) {
+    const int64_t per = (n + nchunks - 1) / nchunks;
+    masks[i] = torch::empty({nchunks * null_mask_chunk_words(per)}, on(dev, torch::kInt64));
+    parts[i] = {n, (int64_t)nchunks, per};
+    return (int64_t)masks[i].data_ptr();
+  }
+};
+
+// K1/K2 (p < 0) and K1/K2+K4 fused (p >= 0: HLL registers from the same
+// read; with `nm` the f32 launch also fills the columns' null lane masks).
 std::tuple<torch::Tensor, torch::Tensor> moments_body(const std::vector<torch::Tensor> &cols,
                                                       const std::vector<double> &shifts,
-                                                      int64_t p, const char *name) {
+                                                      int64_t p, const char *name,
+                                                      NullMasks *nm = nullptr) {
   ColumnBatch all = gather_columns(cols, name, F32 | F64);
   if (!shifts.empty()) check_count(shifts.size(), cols.size(), name, "shifts");
   auto device = all.device;
@@ -207,10 +228,18 @@ std::tuple<torch::Tensor, torch::Tensor> moments_body(const std::vector<torch::T
     auto sub = torch::empty({ncols, 9}, on(device, torch::kFloat64));
     if (hll) {
       reg_sub = torch::zeros({ncols, m}, on(device, torch::kInt32));
+      torch::Tensor dmask;
+      if (nm && b.dtype == 0) {
+        std::vector<int64_t> mptrs;
+        for (int j = 0; j < ncols; ++j) mptrs.push_back(nm->add(b.idx[j], b.lens[j], nchunks, device));
+        dmask = upload(mptrs, device);
+      }
       check_hip(anovos_moments_hll(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
                                    dsh.data_ptr<double>(), ncols, (int)p, nchunks, b.dtype,
                                    partials.data_ptr<double>(), sub.data_ptr<double>(),
-                                   reg_sub.data_ptr<int>(), current_stream()),
+                                   reg_sub.data_ptr<int>(),
+                                   dmask.defined() ? ptr_table<uint64_t>(dmask) : nullptr,
+                                   current_stream()),
                 "anovos_moments_hll");
     } else {
       check_hip(anovos_moments(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(),
@@ -314,11 +343,15 @@ torch::Tensor column_moments(std::vector<torch::Tensor> cols, std::vector<double
 }
 
 // K1/K2+K4 fused: moments + HLL registers in one read.
-// Returns (moments [ncols,9] f64, regs [ncols, 1<<p] i32).
-std::tuple<torch::Tensor, torch::Tensor> moments_hll(std::vector<torch::Tensor> cols, int64_t p,
-                                                     std::vector<double> shifts) {
+// Returns (moments [ncols,9] f64, regs [ncols, 1<<p] i32); with null_masks
+// also (masks, partitions) per column, None / [] for the f64 columns.
+py::object moments_hll(std::vector<torch::Tensor> cols, int64_t p, std::vector<double> shifts,
+                       bool null_masks) {
   TORCH_CHECK(p >= 0, "moments_hll: p must not be negative");
-  return moments_body(cols, shifts, p, "moments_hll");
+  if (!null_masks) return py::cast(moments_body(cols, shifts, p, "moments_hll"));
+  NullMasks nm(cols.size());
+  auto r = moments_body(cols, shifts, p, "moments_hll", &nm);
+  return py::make_tuple(std::get<0>(r), std::get<1>(r), nm.masks, nm.parts);
 }
 
 torch::Tensor column_histograms(std::vector<torch::Tensor> cols, torch::Tensor lo,
@@ -423,6 +456,38 @@ torch::Tensor hll_registers(torch::Tensor x, int64_t p) {
 
 // K10: adds every row's null count into `out`; accepts float32/float64
 // (NaN null) AND int32 dictionary codes (-1 null), one launch per dtype.
+// K10m: adds the row null counts of the columns whose null lane masks are
+// given into `out`; the masks share one partition {n, nchunks, per}.
+void row_null_counts_masked(std::vector<torch::Tensor> masks, std::vector<int64_t> partition,
+                            torch::Tensor out) {
+  const char *name = "row_null_counts_masked";
+  TORCH_CHECK(!masks.empty(), name, ": no columns");
+  check_count(partition.size(), 3, name, "partition");
+  const int64_t n = partition[0], nchunks = partition[1], per = partition[2];
+  TORCH_CHECK(n >= 0 && nchunks >= 1 && nchunks <= INT32_MAX && per == (n + nchunks - 1) / nchunks,
+              name, ": partition is not {n, nchunks, ceil(n / nchunks)}");
+  auto device = masks[0].device();
+  TORCH_CHECK(device.is_cuda(), name, ": device masks required");
+  const int64_t words = nchunks * null_mask_chunk_words(per);
+  std::vector<int64_t> ptrs;
+  for (auto &t : masks) {
+    TORCH_CHECK(t.device() == device && t.is_contiguous() && t.scalar_type() == torch::kInt64, name,
+                ": masks must be contiguous int64 tensors on one device");
+    TORCH_CHECK(t.numel() == words, name, ": a mask has ", t.numel(), " words, its partition needs ",
+                words);
+    // the kernel reads a group as one 32-byte-aligned vector
+    TORCH_CHECK((int64_t)t.data_ptr() % 32 == 0, name, ": masks must be 32-byte aligned");
+    ptrs.push_back((int64_t)t.data_ptr());
+  }
+  TORCH_CHECK(out.device() == device && out.is_contiguous() && out.scalar_type() == torch::kInt32,
+              name, ": out must be a contiguous int32 tensor on the masks' device");
+  TORCH_CHECK(out.numel() == n, name, ": mask/out length mismatch");
+  auto dptr = upload(ptrs, device);
+  check_hip(anovos_row_null_masked(ptr_table<const uint64_t>(dptr), (int)ptrs.size(), n,
+                                   (int)nchunks, per, out.data_ptr<int32_t>(), current_stream()),
+            "anovos_row_null_masked");
+}
+
 void row_null_counts_num(std::vector<torch::Tensor> cols, torch::Tensor out) {
   ColumnBatch all = gather_columns(cols, "row_null_counts_num", F32 | F64 | I32, /*equal_len=*/true);
   check_dense_on_device(out, all, "out", torch::kInt32, all.maxn);
@@ -635,8 +700,11 @@ torch::Tensor centered_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
 }
 
 // K5 fused: multi-column code counts (+ null slot per column).
-// Returns flat int64 tensor of length sum(sizes_i + 1).
-torch::Tensor code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int64_t> sizes) {
+// Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
+// (flat, masks, partitions), where the columns that count in LDS get their
+// null lane masks from the same read and the others None / [].
+py::object code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int64_t> sizes,
+                             bool null_masks) {
   ColumnBatch b = gather_columns(cols, "code_counts_multi", I32);
   check_count(sizes.size(), cols.size(), b.name, "sizes");
   std::vector<int64_t> offs;
@@ -658,12 +726,22 @@ torch::Tensor code_counts_multi(std::vector<torch::Tensor> cols, std::vector<int
   auto dlen = upload(b.lens, b.device);
   auto doff = upload(offs, b.device);
   auto dsz = upload(std::vector<int>(sizes.begin(), sizes.end()), b.device);
+  NullMasks nm(cols.size());
+  torch::Tensor dmask;
+  if (null_masks) {
+    std::vector<int64_t> mptrs;
+    for (int j = 0; j < b.ncols(); ++j)
+      mptrs.push_back(sizes[j] + 1 <= CODE_LDS_SLOTS ? nm.add(j, b.lens[j], nchunks, b.device) : 0);
+    dmask = upload(mptrs, b.device);
+  }
   check_hip(anovos_code_counts_multi(ptr_table<const int32_t>(dptr), dlen.data_ptr<int64_t>(),
                                      doff.data_ptr<int64_t>(), dsz.data_ptr<int>(), b.ncols(),
                                      lds_slots, nchunks, (uint64_t *)out.data_ptr<int64_t>(),
+                                     null_masks ? ptr_table<uint64_t>(dmask) : nullptr,
                                      current_stream()),
             "anovos_code_counts_multi");
-  return out;
+  if (!null_masks) return py::cast(out);
+  return py::make_tuple(out, nm.masks, nm.parts);
 }
 
 // K22: contingency tables of column pairs. The kernel (pair_counts.hip)
@@ -1050,7 +1128,8 @@ std::tuple<torch::Tensor, std::vector<torch::Tensor>> outlier_clamp_columns(
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("code_counts_multi", &code_counts_multi, "fused multi-column code counts + null slot (K5)");
+  m.def("code_counts_multi", &code_counts_multi, "fused multi-column code counts + null slot (K5)",
+        py::arg("cols"), py::arg("sizes"), py::arg("null_masks") = false);
   m.def("pair_code_counts", &pair_code_counts, "contingency tables of code-column pairs (K22)");
   m.def("pair_code_counts_plan", &pair_code_counts_plan,
         "[items, column streams, LDS counters] of a K22 pair list");
@@ -1062,7 +1141,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("label_counts_multi", &label_counts_multi, "fused multi-column label-conditioned histograms (K9)");
   m.def("bucketize_label_counts", &bucketize_label_counts, "fused bucketize + label counts, no binned materialization (K6+K9)");
   m.def("moments_hll", &moments_hll, "fused moments + HLL registers (K1/K2+K4)",
-        py::arg("cols"), py::arg("p"), py::arg("shifts") = std::vector<double>());
+        py::arg("cols"), py::arg("p"), py::arg("shifts") = std::vector<double>(),
+        py::arg("null_masks") = false);
   m.def("centered_gram_bf16", &centered_gram_bf16, "bf16 MFMA centered Gram X^T X (K8)");
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
@@ -1082,4 +1162,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("code_counts", &code_counts, "dictionary code bincount (K5)");
   m.def("hll_registers", &hll_registers, "HyperLogLog registers (K4)");
   m.def("row_null_counts_num", &row_null_counts_num, "fused row null counts (K10)");
+  m.def("row_null_counts_masked", &row_null_counts_masked,
+        "row null counts from null lane masks (K10m)");
 }

@@ -44,6 +44,13 @@ constexpr int RB_MAXB = 16;
 constexpr int LABEL_MAX_SLOTS = 8192;
 // K6 with counts: cutoffs per column (doubles + uint32 counters in LDS)
 constexpr int BKT_COUNTS_MAX_NCUT = 4096;
+// Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
+// chunk of `per` rows owns. A group of four words covers the 256 rows of
+// one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
+// of the scalar tail. A column's mask has nchunks * this many words.
+__host__ __device__ constexpr int64_t null_mask_chunk_words(int64_t per) {
+  return 4 * ((((per >> 2) + 63) >> 6) + 1);
+}
 
 // ---- launchers: return a hipError_t as int, 0 on success ----
 // dtype: 0 = float32 columns, 1 = float64 (K10 also 2 = int32 codes)
@@ -104,7 +111,7 @@ int anovos_fill_code(const int32_t *const *cols, const int64_t *lens, int ncols,
 int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
                              const int64_t *offs, const int *sizes, int ncols,
                              int lds_slots, int nchunks, uint64_t *out,
-                             hipStream_t stream);
+                             uint64_t *const *masks, hipStream_t stream);
 int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
                          int ncols, const double *lo, const double *hi,
                          int nchunks, int mode, int dtype, void *const *outs,
@@ -112,7 +119,15 @@ int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
 int anovos_moments_hll(const void *const *cols, const int64_t *lens,
                        const double *shifts, int ncols, int p, int nchunks,
                        int dtype, double *partials, double *mom_out,
-                       int32_t *regs, hipStream_t stream);
+                       int32_t *regs, uint64_t *const *masks, hipStream_t stream);
+// masks (K5, K1/K2+K4 f32): null, or one pointer per column to
+// nchunks * null_mask_chunk_words(ceil(len / nchunks)) words that receive
+// the column's null lane masks; K5 takes a null entry for a column that
+// counts in global memory. K10m adds the row null counts of columns that
+// share the partition (n, nchunks, per) into out[n].
+int anovos_row_null_masked(const uint64_t *const *masks, int ncols, int64_t n,
+                           int nchunks, int64_t per, int32_t *out,
+                           hipStream_t stream);
 int anovos_bucketize_label_counts(const void *const *cols, const uint8_t *label,
                                   const int64_t *lens, const double *cutflat,
                                   const int64_t *cutoff_off, const int *cutoff_len,

@@ -12,6 +12,9 @@
 //                                registers; moments_hll fuses K1/K2+K4.
 //   K5     code_counts         — dictionary-code bincount, LDS-staged.
 //   K10    row_null_counts     — fused row-wise NaN count across columns.
+//   K10m   row_null_masked     — the same from the null lane masks that
+//                                moments_hll / code_counts_multi can write
+//                                from the read they do anyway.
 //
 // Design notes (cdna_hip_programming.md): wave64; blocks of 256 threads;
 // grids sized ncols x chunks >> 256 workgroups to fill 8 XCDs; fp32 loads
@@ -33,6 +36,56 @@
 // plain float4 on gfx950 (tools/bwbench.hip)
 typedef int nat_i4 __attribute__((ext_vector_type(4)));
 typedef float nat_f4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------
+// Null lane masks: what a 4-wide streaming loop already knows about nulls,
+// written out for K10m at 1 byte per 32 bytes read.
+// ------------------------------------------------------------------
+// The layout is local to a (column, chunk) block and mirrors its loop: the
+// lane with vector index i = 256k + 64w + L (iteration k, wave w, lane L)
+// belongs to group i >> 6. A group is four 64-bit words; bit L of word c
+// says that row s + 4i + c is null, i.e. word c is the lane mask of the
+// compare on component c. Lanes past nv have left the loop and give zero
+// bits. The four waves of a block iteration write one 128-byte line. The
+// <= 3 rows of the scalar tail get the next group, (nv + 63) >> 6, where
+// bit t of word 0 stands for row s + 4 nv + t. A chunk owns
+// null_mask_chunk_words(per) words; words of groups the loop never reaches
+// are not written and not read.
+// A wave's group in iteration k is 4 k + w: its address is the same in all
+// lanes and advances by a constant, which keeps the address arithmetic out
+// of the vector unit.
+DEV_INLINE uint64_t *null_masks_first_group(uint64_t *chunk_words) {
+  return chunk_words + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
+DEV_INLINE void null_masks_store(uint64_t *group, uint64_t b0, uint64_t b1, uint64_t b2,
+                                 uint64_t b3) {
+  if ((threadIdx.x & 63) == 0) {
+    typedef uint64_t nat_u2 __attribute__((ext_vector_type(2)));
+    nat_u2 *g = reinterpret_cast<nat_u2 *>(group);  // 32-byte aligned
+    g[0] = nat_u2{b0, b1};
+    g[1] = nat_u2{b2, b3};
+  }
+}
+
+DEV_INLINE void null_masks_emit(uint64_t *group, bool n0, bool n1, bool n2, bool n3) {
+  null_masks_store(group, __ballot(n0), __ballot(n1), __ballot(n2), __ballot(n3));
+}
+
+// The same from "is a value" flags: the moments test every component for
+// NaN already, and the mask of the nulls is the active lanes that fail it:
+// scalar arithmetic on a compare the loop has anyway.
+DEV_INLINE void null_masks_emit_valid(uint64_t *group, bool v0, bool v1, bool v2, bool v3) {
+  const uint64_t act = __ballot(true);
+  null_masks_store(group, act & ~__ballot(v0), act & ~__ballot(v1), act & ~__ballot(v2),
+                   act & ~__ballot(v3));
+}
+
+// lanes 0..2 of wave 0 are the only ones in a chunk's scalar tail loop
+DEV_INLINE void null_masks_emit_tail(uint64_t *group, bool isnull) {
+  const uint64_t b = __ballot(isnull);
+  if (threadIdx.x == 0) group[0] = b;
+}
 
 // ------------------------------------------------------------------
 // K1/K2: fused column moments
@@ -929,6 +982,96 @@ __global__ __launch_bounds__(THREADS) void row_null_kernel(
 }
 
 // ------------------------------------------------------------------
+// K10m: row null counts from null lane masks (layout at null_masks_emit)
+// instead of the columns: 1 bit per value, not 32.
+// ------------------------------------------------------------------
+// All columns of a launch share one partition (n, nchunks, per). A wave
+// takes one group of one chunk: lane L owns rows s + 256 G + 4 L + 0..3
+// and a counter for each. A group's four words are lane masks, and the wave
+// uses them as such: it reads them with one scalar load per column (their
+// address is the same for all lanes; through the vector path that
+// broadcast cost a full 1 KB request per column and bounded the kernel),
+// and lane L adds bit L of word c to counter c with a select on the mask
+// and an add. The masks are read through the constant address space, which
+// is what lets the compiler pick scalar loads: an earlier launch wrote
+// them and nothing writes them here. Unrolled by NULL_MASK_UNROLL columns
+// to keep their loads in flight. Chunk starts are odd in general, so the
+// read-modify-write of `out` is 4-byte aligned only.
+typedef uint64_t nat_u64x4 __attribute__((ext_vector_type(4)));
+#define NULL_MASK_UNROLL 8
+
+DEV_INLINE nat_u64x4 load_mask_group(const uint64_t *group) {
+  typedef const nat_u64x4 __attribute__((address_space(4))) *const_group;
+  return *(const_group)(uintptr_t)group;  // 32-byte aligned
+}
+
+__global__ __launch_bounds__(THREADS) void row_null_masked_kernel(
+    const uint64_t *const *__restrict__ masks, int ncols, int64_t n, int nchunks, int64_t per,
+    int32_t *__restrict__ out) {
+  const int64_t wpc = null_mask_chunk_words(per);
+  const int64_t gpc = wpc >> 2;  // groups per chunk, the tail's included
+  const int lane = threadIdx.x & 63;
+  // the wave index is the same in all lanes: say so, and what follows stays scalar
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t item = (int64_t)blockIdx.x * (THREADS / 64) + wave;
+  if (item >= gpc * nchunks) return;
+  const int64_t chunk = item / gpc;
+  const int64_t G = item % gpc;
+  const int64_t s = chunk * per;
+  const int64_t e = min(n, s + per);
+  if (e <= s) return;
+  const int64_t nv = (e - s) >> 2;
+  const int64_t gv = (nv + 63) >> 6;
+  const int ntail = (int)((e - s) - 4 * nv);
+  const bool tail = (G == gv);
+  if (G > gv || (tail && ntail == 0)) return;
+
+  const int64_t woff = chunk * wpc + 4 * G;
+  uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+  auto add = [&](nat_u64x4 w) {
+    c0 += __builtin_amdgcn_inverse_ballot_w64(w.x);
+    c1 += __builtin_amdgcn_inverse_ballot_w64(w.y);
+    c2 += __builtin_amdgcn_inverse_ballot_w64(w.z);
+    c3 += __builtin_amdgcn_inverse_ballot_w64(w.w);
+  };
+  int c = 0;
+  for (; c + NULL_MASK_UNROLL <= ncols; c += NULL_MASK_UNROLL) {
+    nat_u64x4 w[NULL_MASK_UNROLL];
+#pragma unroll
+    for (int j = 0; j < NULL_MASK_UNROLL; ++j) w[j] = load_mask_group(masks[c + j] + woff);
+#pragma unroll
+    for (int j = 0; j < NULL_MASK_UNROLL; ++j) add(w[j]);
+  }
+  for (; c < ncols; ++c) add(load_mask_group(masks[c] + woff));
+  if (tail) {
+    // lane t stands for row s + 4 nv + t; only word 0 of the group is written
+    if (lane < ntail) out[s + 4 * nv + lane] += (int32_t)c0;
+    return;
+  }
+  const int64_t q = 64 * G + lane;  // the lane's vector index in the chunk
+  if (q < nv) {
+    int32_t *o = out + s + 4 * q;
+    o[0] += (int32_t)c0;
+    o[1] += (int32_t)c1;
+    o[2] += (int32_t)c2;
+    o[3] += (int32_t)c3;
+  }
+}
+
+extern "C" int anovos_row_null_masked(const uint64_t *const *masks, int ncols, int64_t n,
+                                      int nchunks, int64_t per, int32_t *out,
+                                      hipStream_t stream) {
+  if (n <= 0 || ncols <= 0) return 0;  // empty shard
+  if (nchunks < 1 || per != (n + nchunks - 1) / nchunks) return (int)hipErrorInvalidValue;
+  const int64_t items = (null_mask_chunk_words(per) >> 2) * nchunks;
+  const int64_t blocks = (items + THREADS / 64 - 1) / (THREADS / 64);
+  if (blocks > INT32_MAX) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(row_null_masked_kernel, dim3((uint32_t)blocks), dim3(THREADS), 0, stream,
+                     masks, ncols, n, nchunks, per, out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------
 // K4 fused: multi-column HyperLogLog
 // ------------------------------------------------------------------
 
@@ -1322,10 +1465,16 @@ int anovos_fillnan(const void *const *cols, const int64_t *lens, int ncols,
 // per-column counts land at out[off[col] .. off[col]+size[col]] and the
 // null count (code < 0) at out[off[col]+size[col]]. LDS-staged when the
 // dictionary fits (includes the null slot).
+//
+// MASK: the LDS path also writes the chunk-local null lane masks of
+// null_masks_emit (null = code -1, the rule of row_null_kernel, not the
+// count's "outside [0, size)"); masks[col] is null for a column that
+// counts in global memory, which emits none.
 // ------------------------------------------------------------------
+template <bool MASK>
 __global__ __launch_bounds__(THREADS) void code_counts_multi_kernel(
     const int32_t *const *cols, const int64_t *lens, const int64_t *offs,
-    const int *sizes, int nchunks, uint64_t *out) {
+    const int *sizes, int nchunks, uint64_t *out, uint64_t *const *masks) {
   const int col = blockIdx.x / nchunks;
   const int chunk = blockIdx.x % nchunks;
   const int32_t *__restrict__ codes = cols[col];
@@ -1348,8 +1497,17 @@ __global__ __launch_bounds__(THREADS) void code_counts_multi_kernel(
     // loads are 1/4 the per-instruction bytes of dwordx4)
     const int64_t nv = (e - s) / 4;
     const nat_i4 *__restrict__ cv = reinterpret_cast<const nat_i4 *>(codes + s);
+    uint64_t *mrow = nullptr, *mgroup = nullptr;
+    if (MASK) {
+      mrow = masks[col] + (int64_t)chunk * null_mask_chunk_words(per);
+      mgroup = null_masks_first_group(mrow);
+    }
     for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
       nat_i4 c = __builtin_nontemporal_load(&cv[i]);
+      if (MASK) {
+        null_masks_emit(mgroup, c.x == -1, c.y == -1, c.z == -1, c.w == -1);
+        mgroup += 4 * (THREADS / 64);
+      }
       atomicAdd(&cnt[(c.x >= 0 && c.x < size) ? c.x : size], 1u);
       atomicAdd(&cnt[(c.y >= 0 && c.y < size) ? c.y : size], 1u);
       atomicAdd(&cnt[(c.z >= 0 && c.z < size) ? c.z : size], 1u);
@@ -1357,6 +1515,7 @@ __global__ __launch_bounds__(THREADS) void code_counts_multi_kernel(
     }
     for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += THREADS) {
       int c = codes[i];
+      if (MASK) null_masks_emit_tail(mrow + 4 * ((nv + 63) >> 6), c == -1);
       atomicAdd(&cnt[(c >= 0 && c < size) ? c : size], 1u);
     }
     __syncthreads();
@@ -1487,14 +1646,19 @@ extern "C" {
 int anovos_code_counts_multi(const int32_t *const *cols, const int64_t *lens,
                              const int64_t *offs, const int *sizes, int ncols,
                              int lds_slots, int nchunks, uint64_t *out,
-                             hipStream_t stream) {
+                             uint64_t *const *masks, hipStream_t stream) {
   // lds_slots: the most slots (sizes[c] + 1) among the columns that stage
   // their counters in LDS (<= 16384 slots); 0 when none does
   if (lds_slots < 0 || lds_slots > CODE_LDS_SLOTS) return (int)hipErrorInvalidValue;
   size_t lds = (size_t)lds_slots * 4;
-  hipLaunchKernelGGL(code_counts_multi_kernel, dim3(ncols * nchunks),
-                     dim3(THREADS), lds, stream, cols, lens, offs, sizes,
-                     nchunks, out);
+  if (masks)
+    hipLaunchKernelGGL(code_counts_multi_kernel<true>, dim3(ncols * nchunks),
+                       dim3(THREADS), lds, stream, cols, lens, offs, sizes,
+                       nchunks, out, masks);
+  else
+    hipLaunchKernelGGL(code_counts_multi_kernel<false>, dim3(ncols * nchunks),
+                       dim3(THREADS), lds, stream, cols, lens, offs, sizes,
+                       nchunks, out, masks);
   return (int)hipGetLastError();
 }
 
@@ -1522,11 +1686,17 @@ int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
 // partials and the HyperLogLog registers (moments and distinct-count
 // are the two prior-free full-frame passes of the analyzer — the
 // equal-width histogram can't join: its range comes FROM the moments).
+//
+// MASK (f32 only): the same read also writes the chunk-local null lane
+// masks of null_masks_emit, which K10m turns into row null counts without
+// a second frame read. The loop, its thread-to-row mapping and every
+// accumulation are the same with and without it.
 // ------------------------------------------------------------------
-template <typename T>
+template <typename T, bool MASK>
 __global__ __launch_bounds__(THREADS) void moments_hll_kernel(
     const T *const *cols, const int64_t *lens, const double *shifts, int p,
-    int nchunks, double *partials, int32_t *regs /*[ncols][1<<p]*/) {
+    int nchunks, double *partials, int32_t *regs /*[ncols][1<<p]*/,
+    uint64_t *const *masks) {
   extern __shared__ int32_t sreg[];  // 1<<p
   const int m = 1 << p;
   const int col = blockIdx.x / nchunks;
@@ -1550,14 +1720,26 @@ __global__ __launch_bounds__(THREADS) void moments_hll_kernel(
   if (sizeof(T) == 4) {
     const int64_t nv = (e - s) / 4;
     const float4 *xv = reinterpret_cast<const float4 *>(x + s);
+    uint64_t *mrow = nullptr, *mgroup = nullptr;
+    if (MASK) {
+      mrow = masks[col] + (int64_t)chunk * null_mask_chunk_words(per);
+      mgroup = null_masks_first_group(mrow);
+    }
     for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
       float4 v = xv[i];
+      if (MASK) {
+        null_masks_emit_valid(mgroup, !isnan(v.x), !isnan(v.y), !isnan(v.z), !isnan(v.w));
+        mgroup += 4 * (THREADS / 64);
+      }
       body((T)v.x);
       body((T)v.y);
       body((T)v.z);
       body((T)v.w);
     }
-    for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += THREADS) body(x[i]);
+    for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += THREADS) {
+      if (MASK) null_masks_emit_tail(mrow + 4 * ((nv + 63) >> 6), isnan((float)x[i]));
+      body(x[i]);
+    }
   } else {
     for (int64_t i = s + threadIdx.x; i < e; i += THREADS) body(x[i]);
   }
@@ -1574,15 +1756,22 @@ extern "C" int anovos_moments_hll(const void *const *cols, const int64_t *lens,
                                   const double *shifts, int ncols, int p,
                                   int nchunks, int dtype, double *partials,
                                   double *mom_out, int32_t *regs,
-                                  hipStream_t stream) {
+                                  uint64_t *const *masks, hipStream_t stream) {
   dim3 grid(ncols * nchunks);
   size_t lds = (size_t)(1 << p) * 4;
-  if (dtype == 0)
-    hipLaunchKernelGGL(moments_hll_kernel<float>, grid, dim3(THREADS), lds, stream,
-                       (const float *const *)cols, lens, shifts, p, nchunks, partials, regs);
+  if (masks && dtype != 0) return (int)hipErrorInvalidValue;  // f32 only
+  if (masks)
+    hipLaunchKernelGGL((moments_hll_kernel<float, true>), grid, dim3(THREADS), lds, stream,
+                       (const float *const *)cols, lens, shifts, p, nchunks, partials, regs,
+                       masks);
+  else if (dtype == 0)
+    hipLaunchKernelGGL((moments_hll_kernel<float, false>), grid, dim3(THREADS), lds, stream,
+                       (const float *const *)cols, lens, shifts, p, nchunks, partials, regs,
+                       masks);
   else
-    hipLaunchKernelGGL(moments_hll_kernel<double>, grid, dim3(THREADS), lds, stream,
-                       (const double *const *)cols, lens, shifts, p, nchunks, partials, regs);
+    hipLaunchKernelGGL((moments_hll_kernel<double, false>), grid, dim3(THREADS), lds, stream,
+                       (const double *const *)cols, lens, shifts, p, nchunks, partials, regs,
+                       masks);
   hipLaunchKernelGGL(moments_reduce_kernel, dim3(ncols), dim3(THREADS), 0, stream,
                      partials, nchunks, mom_out);
   return (int)hipGetLastError();
