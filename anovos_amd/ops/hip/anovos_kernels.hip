@@ -37,6 +37,41 @@
 typedef int nat_i4 __attribute__((ext_vector_type(4)));
 typedef float nat_f4 __attribute__((ext_vector_type(4)));
 
+// Column pointers reach a kernel through a device pointer table, which
+// hides their address space: loads through them compile to flat
+// instructions, which count on the LDS counter as well, so a loop that also
+// reads or updates LDS waits for its column loads with every LDS wait. The
+// read-only kernels that keep a load in flight across their LDS work
+// (moments_hll, code_counts_multi, label_counts_multi) cast the pointer once
+// per block to the global address space, as corr_mfma.hip and
+// grouped_moments.hip do. The read + write loops touch no LDS between load
+// and store and measured the same either way (tools/bwbench.hip), so they
+// keep plain pointers. No alignment is implied beyond the element's:
+// dwordx4 accesses at x + s stay 4-byte aligned only.
+#define GLOBAL_AS __attribute__((address_space(1)))
+typedef const nat_f4 GLOBAL_AS *gin_f4;
+typedef const nat_i4 GLOBAL_AS *gin_i4;
+
+// Block -> (column, chunk) of an ncols x nchunks launch, chunk-major: the
+// blocks in flight at one time stream the same row range of neighbouring
+// columns. With the column-major order (col = blockIdx.x / nchunks) the
+// ~2048 resident blocks sat one multi-megabyte chunk apart inside a few
+// columns, and a 150-column copy ran at 4.7 TB/s instead of 5.4
+// (tools/bwbench.hip, profiles/streaming_global_ab.md). What a (column,
+// chunk) pair computes does not depend on which block takes it.
+DEV_INLINE int block_column(int nchunks) { return blockIdx.x % (gridDim.x / nchunks); }
+DEV_INLINE int block_chunk(int nchunks) { return blockIdx.x / (gridDim.x / nchunks); }
+
+// Rows per chunk, ceil(n / nchunks): the one definition every kernel and the
+// null-mask layout share (the launcher of K10m checks the same value on the
+// host). Frames below 2^32 rows take a 32-bit division; the 64-bit one is
+// ~150 scalar instructions per block.
+DEV_INLINE int64_t chunk_rows(int64_t n, int nchunks) {
+  const uint64_t t = (uint64_t)n + (uint64_t)(nchunks - 1);
+  if (t <= 0xFFFFFFFFull) return (int64_t)((uint32_t)t / (uint32_t)nchunks);
+  return (int64_t)(t / (uint64_t)nchunks);
+}
+
 // ------------------------------------------------------------------
 // Null lane masks: what a 4-wide streaming loop already knows about nulls,
 // written out for K10m at 1 byte per 32 bytes read.
@@ -54,35 +89,40 @@ typedef float nat_f4 __attribute__((ext_vector_type(4)));
 // A wave's group in iteration k is 4 k + w: its address is the same in all
 // lanes and advances by a constant, which keeps the address arithmetic out
 // of the vector unit.
-DEV_INLINE uint64_t *null_masks_first_group(uint64_t *chunk_words) {
+// Mask words are written through global address-space pointers, like the
+// columns: a flat store inside a streaming loop would put the loop's LDS
+// waits behind it.
+typedef uint64_t GLOBAL_AS *gmask;
+
+DEV_INLINE gmask null_masks_first_group(gmask chunk_words) {
   return chunk_words + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
 
-DEV_INLINE void null_masks_store(uint64_t *group, uint64_t b0, uint64_t b1, uint64_t b2,
+DEV_INLINE void null_masks_store(gmask group, uint64_t b0, uint64_t b1, uint64_t b2,
                                  uint64_t b3) {
   if ((threadIdx.x & 63) == 0) {
     typedef uint64_t nat_u2 __attribute__((ext_vector_type(2)));
-    nat_u2 *g = reinterpret_cast<nat_u2 *>(group);  // 32-byte aligned
+    nat_u2 GLOBAL_AS *g = (nat_u2 GLOBAL_AS *)group;  // 32-byte aligned
     g[0] = nat_u2{b0, b1};
     g[1] = nat_u2{b2, b3};
   }
 }
 
-DEV_INLINE void null_masks_emit(uint64_t *group, bool n0, bool n1, bool n2, bool n3) {
+DEV_INLINE void null_masks_emit(gmask group, bool n0, bool n1, bool n2, bool n3) {
   null_masks_store(group, __ballot(n0), __ballot(n1), __ballot(n2), __ballot(n3));
 }
 
 // The same from "is a value" flags: the moments test every component for
 // NaN already, and the mask of the nulls is the active lanes that fail it:
 // scalar arithmetic on a compare the loop has anyway.
-DEV_INLINE void null_masks_emit_valid(uint64_t *group, bool v0, bool v1, bool v2, bool v3) {
+DEV_INLINE void null_masks_emit_valid(gmask group, bool v0, bool v1, bool v2, bool v3) {
   const uint64_t act = __ballot(true);
   null_masks_store(group, act & ~__ballot(v0), act & ~__ballot(v1), act & ~__ballot(v2),
                    act & ~__ballot(v3));
 }
 
 // lanes 0..2 of wave 0 are the only ones in a chunk's scalar tail loop
-DEV_INLINE void null_masks_emit_tail(uint64_t *group, bool isnull) {
+DEV_INLINE void null_masks_emit_tail(gmask group, bool isnull) {
   const uint64_t b = __ballot(isnull);
   if (threadIdx.x == 0) group[0] = b;
 }
@@ -173,7 +213,7 @@ __global__ __launch_bounds__(THREADS) void moments_partials_kernel(
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
   const double shift = shifts ? shifts[col] : 0.0;
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
@@ -241,14 +281,14 @@ __global__ __launch_bounds__(THREADS) void hist_kernel(
     const T *const *cols, const int64_t *lens, const double *lo, const double *hi,
     int nbins, int nchunks, uint64_t *out /*[ncols][nbins]*/) {
   extern __shared__ uint32_t bins[];  // nbins
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   for (int b = threadIdx.x; b < nbins; b += THREADS) bins[b] = 0;
   __syncthreads();
 
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const double l = lo[col];
@@ -304,7 +344,7 @@ __global__ __launch_bounds__(THREADS) void bracket_hist_kernel(
   const int col = (int)colidx[bracket];
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const double l = lo[bracket];
@@ -369,7 +409,7 @@ __global__ __launch_bounds__(THREADS) void bracket_hist_grouped_kernel(
   __syncthreads();
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
@@ -425,7 +465,7 @@ __global__ __launch_bounds__(THREADS) void bucketize_kernel(
   const T *__restrict__ x = cols[col];
   int32_t *__restrict__ out = outs[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   for (int64_t i = s + threadIdx.x; i < e; i += THREADS) {
@@ -497,8 +537,8 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
     int nchunks, float *const *outs, int max_ncut, uint64_t *counts,
     const int64_t *count_off) {
   extern __shared__ double cuts[];
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int ncut = cutoff_len[col];
   uint32_t *cnt = nullptr;   // [max_ncut + 2] block-shared counters
   uint32_t *priv = nullptr;  // this thread's private row (private mode)
@@ -536,7 +576,7 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
   const T *__restrict__ x = cols[col];
   float *__restrict__ out = outs[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
@@ -659,13 +699,13 @@ __global__ __launch_bounds__(THREADS) void bucketize_float_kernel(
 __global__ __launch_bounds__(THREADS) void lut_apply_f32_kernel(
     const int32_t *const *cols, const int64_t *lens, const float *lutflat,
     const int64_t *lut_off, int nchunks, float *const *outs) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int32_t *__restrict__ codes = cols[col];
   float *__restrict__ out = outs[col];
   const float *__restrict__ lut = &lutflat[lut_off[col]];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const nat_i4 *__restrict__ cv = reinterpret_cast<const nat_i4 *>(codes + s);
@@ -690,13 +730,13 @@ __global__ __launch_bounds__(THREADS) void lut_apply_f32_kernel(
 __global__ __launch_bounds__(THREADS) void lut_apply_i32_kernel(
     const int32_t *const *cols, const int64_t *lens, const int32_t *lutflat,
     const int64_t *lut_off, int nchunks, int32_t *const *outs) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int32_t *__restrict__ codes = cols[col];
   int32_t *__restrict__ out = outs[col];
   const int32_t *__restrict__ lut = &lutflat[lut_off[col]];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const nat_i4 *__restrict__ cv = reinterpret_cast<const nat_i4 *>(codes + s);
@@ -723,13 +763,13 @@ __global__ __launch_bounds__(THREADS) void lut_apply_i32_kernel(
 __global__ __launch_bounds__(THREADS) void fill_code_kernel(
     const int32_t *const *cols, const int64_t *lens, const int32_t *fill,
     int nchunks, int32_t *const *outs) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int32_t *__restrict__ x = cols[col];
   int32_t *__restrict__ out = outs[col];
   const int64_t n = lens[col];
   const int32_t fv = fill[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const nat_i4 *__restrict__ xv = reinterpret_cast<const nat_i4 *>(x + s);
@@ -777,7 +817,7 @@ __global__ __launch_bounds__(THREADS) void code_counts_kernel(
     __syncthreads();
   }
   const int chunk = blockIdx.x;
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   if (use_lds) {
@@ -858,7 +898,7 @@ __global__ __launch_bounds__(THREADS) void hll_kernel(
   for (int i = threadIdx.x; i < m; i += THREADS) sreg[i] = 0;
   __syncthreads();
   const int chunk = blockIdx.x;
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   if (sizeof(T) == 4) {
@@ -1087,7 +1127,7 @@ __global__ __launch_bounds__(THREADS) void hll_multi_kernel(
   __syncthreads();
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   if (sizeof(T) == 4) {
@@ -1126,12 +1166,12 @@ template <typename T>
 __global__ __launch_bounds__(THREADS) void axpb_kernel(
     const T *const *cols, const int64_t *lens, const double *a, const double *b,
     int nchunks, float *const *outs) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const T *__restrict__ x = cols[col];
   float *__restrict__ out = outs[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const float av = (float)a[col];
@@ -1168,12 +1208,12 @@ template <typename T>
 __global__ __launch_bounds__(THREADS) void fillnan_kernel(
     const T *const *cols, const int64_t *lens, const double *fill, int nchunks,
     T *const *outs) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const T *__restrict__ x = cols[col];
   T *__restrict__ out = outs[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   const T fv = (T)fill[col];
@@ -1475,8 +1515,8 @@ template <bool MASK>
 __global__ __launch_bounds__(THREADS) void code_counts_multi_kernel(
     const int32_t *const *cols, const int64_t *lens, const int64_t *offs,
     const int *sizes, int nchunks, uint64_t *out, uint64_t *const *masks) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int32_t *__restrict__ codes = cols[col];
   const int64_t n = lens[col];
   const int size = sizes[col];
@@ -1489,21 +1529,26 @@ __global__ __launch_bounds__(THREADS) void code_counts_multi_kernel(
     for (int i = threadIdx.x; i < slots; i += THREADS) cnt[i] = 0;
     __syncthreads();
   }
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   if (use_lds) {
     // int4 vectorized reads (the scalar loop measured ~3.3 TB/s; dword
     // loads are 1/4 the per-instruction bytes of dwordx4)
     const int64_t nv = (e - s) / 4;
-    const nat_i4 *__restrict__ cv = reinterpret_cast<const nat_i4 *>(codes + s);
-    uint64_t *mrow = nullptr, *mgroup = nullptr;
+    const gin_i4 cv = (gin_i4)(codes + s);
+    gmask mrow = nullptr, mgroup = nullptr;
     if (MASK) {
-      mrow = masks[col] + (int64_t)chunk * null_mask_chunk_words(per);
+      mrow = (gmask)masks[col] + (int64_t)chunk * null_mask_chunk_words(per);
       mgroup = null_masks_first_group(mrow);
     }
-    for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
-      nat_i4 c = __builtin_nontemporal_load(&cv[i]);
+    // the next vector is in flight while this one goes through the counters
+    int64_t i = threadIdx.x;
+    nat_i4 nx = {0, 0, 0, 0};
+    if (i < nv) nx = __builtin_nontemporal_load(&cv[i]);
+    for (; i < nv; i += THREADS) {
+      const nat_i4 c = nx;
+      if (i + THREADS < nv) nx = __builtin_nontemporal_load(&cv[i + THREADS]);
       if (MASK) {
         null_masks_emit(mgroup, c.x == -1, c.y == -1, c.z == -1, c.w == -1);
         mgroup += 4 * (THREADS / 64);
@@ -1541,14 +1586,14 @@ __global__ __launch_bounds__(THREADS) void outlier_clamp_kernel(
     const T *const *cols, const int64_t *lens, const double *lo,
     const double *hi, int nchunks, int mode, T *const *outs,
     uint64_t *counts) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const T *__restrict__ x = cols[col];
   T *__restrict__ y = outs ? outs[col] : nullptr;
   const int64_t n = lens[col];
   const double l = lo[col], h = hi[col];
   const bool has_l = !isnan(l), has_h = !isnan(h);
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
@@ -1692,6 +1737,54 @@ int anovos_outlier_clamp(const void *const *cols, const int64_t *lens,
 // a second frame read. The loop, its thread-to-row mapping and every
 // accumulation are the same with and without it.
 // ------------------------------------------------------------------
+// The f32 loop keeps per lane what fp64 does not have to carry: n, zeros and
+// n_frac are integer counters and min / max stay in f32 (widening is exact).
+// Only the four power sums are fp64.
+struct MomAccF32 {
+  double s1, s2, s3, s4;
+  float mn, mx;
+  uint32_t n, zn, nf;
+};
+
+// One element, predicated on `ok` (not NaN) instead of branched: nulls are
+// about 1 % of the rows, so a branch hardly ever skips anything. The power
+// sums are written out as the operations moments_hll has always compiled to
+// (d2 rounded once, then one fma per sum), so their bits do not rest on the
+// compiler's contraction choices. A null adds d = -0.0, which leaves all four
+// sums as they are: x + (-0.0) == x for every x, and the products fed to the
+// fma are then -0.0 * -0.0 = +0.0 for s2 / s4 (sums of squares, never -0.0)
+// and -0.0 * +0.0 = -0.0 for s3.
+DEV_INLINE void mom_add_f32(MomAccF32 &a, float f, bool ok, double shift) {
+  const double d = ok ? (double)f - shift : -0.0;
+  const double d2 = d * d;
+  a.s1 += d;
+  a.s2 = fma(d, d, a.s2);
+  a.s3 = fma(d, d2, a.s3);
+  a.s4 = fma(d2, d2, a.s4);
+  // fminf / fmaxf return the other operand for a quiet NaN, which is what
+  // the canonical form of any NaN is: no select needed
+  const float fc = __builtin_canonicalizef(f);
+  a.mn = fminf(a.mn, fc);
+  a.mx = fmaxf(a.mx, fc);
+  a.n += ok ? 1u : 0u;
+  a.zn += (f == 0.0f) ? 1u : 0u;
+  a.nf += (ok && f != truncf(f)) ? 1u : 0u;
+}
+
+// fmix32 register index and rho of one f32 value. rho = leading zeros of
+// the 32 - p remainder bits + 1, capped at 32 - p + 1: the guard bit below
+// the remainder stops the count exactly at the cap when the remainder is 0
+// and lies below the leading one otherwise.
+DEV_INLINE void hll_hash_f32(float f, int p, uint32_t guard, int &idx, int &rho) {
+  const uint32_t h = fmix32(__float_as_uint(f));
+  idx = (int)(h >> (32 - p));
+  rho = __builtin_clz((h << p) | guard) + 1;  // guard != 0
+}
+
+// iterations after which the integer lane counters move to fp64: 4 counts
+// per iteration at most, so they stay below 2^26
+#define MOM_FLUSH_ITERS (1 << 24)
+
 template <typename T, bool MASK>
 __global__ __launch_bounds__(THREADS) void moments_hll_kernel(
     const T *const *cols, const int64_t *lens, const double *shifts, int p,
@@ -1699,54 +1792,99 @@ __global__ __launch_bounds__(THREADS) void moments_hll_kernel(
     uint64_t *const *masks) {
   extern __shared__ int32_t sreg[];  // 1<<p
   const int m = 1 << p;
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   for (int i = threadIdx.x; i < m; i += THREADS) sreg[i] = 0;
   __syncthreads();
 
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
   const double shift = shifts ? shifts[col] : 0.0;
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
   MomAcc a{0, 0, 0, 0, 0, (double)INFINITY, -(double)INFINITY, 0};
-  auto body = [&](T v) {
-    mom_add(a, (double)v, shift);
-    int idx, rho;
-    if (hll_hash(v, p, idx, rho)) { if (sreg[idx] < rho) atomicMax(&sreg[idx], rho); }
-  };
   if (sizeof(T) == 4) {
     const int64_t nv = (e - s) / 4;
-    const float4 *xv = reinterpret_cast<const float4 *>(x + s);
-    uint64_t *mrow = nullptr, *mgroup = nullptr;
+    const gin_f4 xv = (gin_f4)(x + s);
+    gmask mrow = nullptr, mgroup = nullptr;
     if (MASK) {
-      mrow = masks[col] + (int64_t)chunk * null_mask_chunk_words(per);
+      mrow = (gmask)masks[col] + (int64_t)chunk * null_mask_chunk_words(per);
       mgroup = null_masks_first_group(mrow);
     }
-    for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
-      float4 v = xv[i];
+    MomAccF32 c{0, 0, 0, 0, INFINITY, -INFINITY, 0, 0, 0};
+    const uint32_t guard = 1u << (p > 0 ? p - 1 : 0);
+    auto flush_counts = [&]() {
+      a.n += (double)c.n;
+      a.zn += (double)c.zn;
+      a.nf += (double)c.nf;
+      c.n = c.zn = c.nf = 0;
+    };
+    auto hll_one = [&](float f, bool ok) {
+      int idx, rho;
+      hll_hash_f32(f, p, guard, idx, rho);
+      if (ok && sreg[idx] < rho) atomicMax(&sreg[idx], rho);
+    };
+    // Thread t takes vectors t, t + 256, ... in this order, as it always
+    // did; the load of the next one is in flight while one is consumed.
+    int64_t i = threadIdx.x;
+    nat_f4 nx = {0.f, 0.f, 0.f, 0.f};
+    if (i < nv) nx = __builtin_nontemporal_load(&xv[i]);
+    int iters = 0;
+    for (; i < nv; i += THREADS) {
+      const nat_f4 v = nx;
+      if (i + THREADS < nv) nx = __builtin_nontemporal_load(&xv[i + THREADS]);
+      // one NaN predicate per element, for masks, moments and registers
+      const bool ok[4] = {v.x == v.x, v.y == v.y, v.z == v.z, v.w == v.w};
+      const float f[4] = {v.x, v.y, v.z, v.w};
       if (MASK) {
-        null_masks_emit_valid(mgroup, !isnan(v.x), !isnan(v.y), !isnan(v.z), !isnan(v.w));
+        null_masks_emit_valid(mgroup, ok[0], ok[1], ok[2], ok[3]);
         mgroup += 4 * (THREADS / 64);
       }
-      body((T)v.x);
-      body((T)v.y);
-      body((T)v.z);
-      body((T)v.w);
+      // the four register reads go out together and are waited for once
+      int idx[4], rho[4], old[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        hll_hash_f32(f[k], p, guard, idx[k], rho[k]);
+        old[k] = sreg[idx[k]];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) mom_add_f32(c, f[k], ok[k], shift);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (ok[k] && old[k] < rho[k]) atomicMax(&sreg[idx[k]], rho[k]);
+      if (++iters == MOM_FLUSH_ITERS) {
+        flush_counts();
+        iters = 0;
+      }
     }
-    for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += THREADS) {
-      if (MASK) null_masks_emit_tail(mrow + 4 * ((nv + 63) >> 6), isnan((float)x[i]));
-      body(x[i]);
+    for (int64_t j = s + nv * 4 + threadIdx.x; j < e; j += THREADS) {
+      const float f = (float)x[j];
+      const bool ok = f == f;
+      if (MASK) null_masks_emit_tail(mrow + 4 * ((nv + 63) >> 6), !ok);
+      mom_add_f32(c, f, ok, shift);
+      hll_one(f, ok);
     }
+    flush_counts();
+    a.s1 = c.s1;
+    a.s2 = c.s2;
+    a.s3 = c.s3;
+    a.s4 = c.s4;
+    a.mn = (double)c.mn;
+    a.mx = (double)c.mx;
   } else {
-    for (int64_t i = s + threadIdx.x; i < e; i += THREADS) body(x[i]);
+    for (int64_t i = s + threadIdx.x; i < e; i += THREADS) {
+      const T v = x[i];
+      mom_add(a, (double)v, shift);
+      int idx, rho;
+      if (hll_hash(v, p, idx, rho)) { if (sreg[idx] < rho) atomicMax(&sreg[idx], rho); }
+    }
   }
 
   // moment block-reduce: wave shuffles + 4-slot LDS (keeps the block's
   // LDS at the 16 KB HLL registers -> ~8 blocks/CU occupancy)
-  mom_block_reduce_write(a, &partials[(int64_t)blockIdx.x * NSTAT]);
+  mom_block_reduce_write(a, &partials[((int64_t)col * nchunks + chunk) * NSTAT]);
   int32_t *g = &regs[(int64_t)col * m];
   for (int i = threadIdx.x; i < m; i += THREADS)
     if (sreg[i]) atomicMax(&g[i], sreg[i]);
@@ -1802,8 +1940,8 @@ __global__ __launch_bounds__(THREADS) void label_counts_multi_kernel(
     const void *const *cols, const uint8_t *__restrict__ label,
     const int64_t *lens, const int64_t *offs, const int *sizes,
     const int *dtypes, int nchunks, uint64_t *out) {
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int slots = sizes[col];
   uint64_t *base = out + offs[col];
   extern __shared__ uint32_t lds2[];  // [2*slots]: totals then events
@@ -1812,15 +1950,20 @@ __global__ __launch_bounds__(THREADS) void label_counts_multi_kernel(
   for (int i = threadIdx.x; i < 2 * slots; i += THREADS) lds2[i] = 0;
   __syncthreads();
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
   if (dtypes[col] == 0) {
     const float *__restrict__ x = (const float *)cols[col];
     const int64_t nv = (e - s) / 4;
-    const nat_f4 *__restrict__ xv = reinterpret_cast<const nat_f4 *>(x + s);
-    for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
-      nat_f4 v = __builtin_nontemporal_load(&xv[i]);
+    const gin_f4 xv = (gin_f4)(x + s);
+    // the next vector is in flight while this one goes through the counters
+    int64_t i = threadIdx.x;
+    nat_f4 nx = {0.f, 0.f, 0.f, 0.f};
+    if (i < nv) nx = __builtin_nontemporal_load(&xv[i]);
+    for (; i < nv; i += THREADS) {
+      const nat_f4 v = nx;
+      if (i + THREADS < nv) nx = __builtin_nontemporal_load(&xv[i + THREADS]);
       const int64_t r = s + i * 4;
       float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -1838,9 +1981,13 @@ __global__ __launch_bounds__(THREADS) void label_counts_multi_kernel(
   } else {
     const int32_t *__restrict__ codes = (const int32_t *)cols[col];
     const int64_t nv = (e - s) / 4;
-    const nat_i4 *__restrict__ cv = reinterpret_cast<const nat_i4 *>(codes + s);
-    for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
-      nat_i4 c = __builtin_nontemporal_load(&cv[i]);
+    const gin_i4 cv = (gin_i4)(codes + s);
+    int64_t i = threadIdx.x;
+    nat_i4 nx = {0, 0, 0, 0};
+    if (i < nv) nx = __builtin_nontemporal_load(&cv[i]);
+    for (; i < nv; i += THREADS) {
+      const nat_i4 c = nx;
+      if (i + THREADS < nv) nx = __builtin_nontemporal_load(&cv[i + THREADS]);
       const int64_t r = s + i * 4;
       int cc[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
@@ -1894,8 +2041,8 @@ __global__ __launch_bounds__(THREADS) void bucketize_label_counts_kernel(
     const int *cutoff_len, const int64_t *offs, const int *sizes,
     int max_ncut, int max_slots, int nchunks, uint64_t *out) {
   extern __shared__ double smem[];
-  const int col = blockIdx.x / nchunks;
-  const int chunk = blockIdx.x % nchunks;
+  const int col = block_column(nchunks);
+  const int chunk = block_chunk(nchunks);
   const int ncut = cutoff_len[col];
   const int slots = sizes[col];
   double *cuts = smem;  // [max_ncut] doubles (f32 path reuses as floats)
@@ -1921,7 +2068,7 @@ __global__ __launch_bounds__(THREADS) void bucketize_label_counts_kernel(
 
   const T *__restrict__ x = cols[col];
   const int64_t n = lens[col];
-  const int64_t per = (n + nchunks - 1) / nchunks;
+  const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
 
