@@ -1,7 +1,8 @@
 """Attribute associations — parity with reference
 data_analyzer/association_evaluator.py (586 LoC).
 
-- correlation_matrix (:38): bf16 MFMA Gram kernel / rocBLAS path (K8),
+- correlation_matrix (:38): bf16 MFMA Gram kernel / rocBLAS path (K8);
+  method="spearman" (beyond the reference) ranks on a grid first (K24),
 - variable_clustering (:142): one fused covariance pass + driver-side
   VarClusHi (association_eval_varclus.py),
 - IV_calculation (:253): per-bin label histograms (K9) + WOE/IV sums,
@@ -32,12 +33,13 @@ from anovos_amd.data_transformer.transformers import (
     _event_indicator,
 )
 from anovos_amd.ops import corr as corr_ops
+from anovos_amd.ops import rank as rank_ops
 from anovos_amd.shared.utils import attributeType_segregation, normalize_columns
 from anovos_amd.shared.tracing import traced
 
 
 @traced
-def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=False, sample_size=1000000, print_impact=False, use_bf16=True):
+def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=False, sample_size=1000000, print_impact=False, use_bf16=True, method="pearson", rank_cells=1024):
     """[attribute, <cols...>] — reference association_evaluator.py:38-139.
 
     use_bf16=True (default) runs the hand-written bf16 MFMA Gram kernel:
@@ -45,7 +47,22 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
     giving up to ~1e-2 relative error on correlation entries vs the
     reference's exact fp64 MLlib corr. Pass use_bf16=False for the f32
     rocBLAS path (centered in f64, ~1e-6). Accumulation is fp32 either
-    way; cross-rank merge is fp64."""
+    way; cross-rank merge is fp64.
+
+    method="spearman" (the reference has no `method`) returns Spearman's
+    rank correlation instead: Pearson's r of the columns' mid-ranks on a
+    grid of `rank_cells` cells per column (2 .. 4096, see ops/rank.py),
+    through the same Gram paths. Ranks are taken among a column's non-null
+    rows and a null takes the mean rank, so it contributes zero — the
+    Pearson path's convention. Rows that share a cell are tied; a column
+    with at most `rank_cells` distinct values or rows is ranked exactly."""
+    if method not in ("pearson", "spearman"):
+        raise TypeError("Invalid input for method: 'pearson' or 'spearman'")
+    if (
+        isinstance(rank_cells, bool) or not isinstance(rank_cells, (int, np.integer))
+        or not 2 <= rank_cells <= rank_ops.GRADE_MAX_CELLS
+    ):
+        raise TypeError(f"Invalid input for rank_cells: an integer in [2, {rank_ops.GRADE_MAX_CELLS}]")
     num_cols = attributeType_segregation(idf)[0]
     if list_of_cols == "all":
         list_of_cols = num_cols
@@ -57,7 +74,10 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
         from anovos_amd.data_ingest.data_sampling import data_sample
 
         idf = data_sample(idf, fraction=float(sample_size) / idf.count(), method_type="random")
-    corr = corr_ops.pearson_matrix(idf, cols, use_bf16=use_bf16)
+    if method == "spearman":
+        corr = rank_ops.spearman_matrix(idf, cols, cells=int(rank_cells), use_bf16=use_bf16)
+    else:
+        corr = corr_ops.pearson_matrix(idf, cols, use_bf16=use_bf16)
     odf = pd.DataFrame(corr, columns=cols, index=cols)
     odf["attribute"] = odf.index
     sorted_cols = sorted(cols)

@@ -1,5 +1,5 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
-// corr_mfma.hip, pair_counts.hip, grouped_moments.hip). Compiled by torch.utils.cpp_extension
+// corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip). Compiled by torch.utils.cpp_extension
 // with hipcc for gfx950; streams come from the caller's current torch HIP
 // stream so kernels compose with the engine's side-stream overlap
 // (core/dist.py SideStream).
@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "anovos_kernels.h"
@@ -1127,8 +1128,113 @@ std::tuple<torch::Tensor, std::vector<torch::Tensor>> outlier_clamp_columns(
   return {counts, outs};
 }
 
+namespace {
+
+// K24 cutoffs: one list per column, at most GRADE_MAX_CELLS - 1 entries,
+// strictly ascending, no NaN.
+void check_grade_cutoffs(const std::vector<torch::Tensor> &cutoffs, size_t ncols, const char *name) {
+  check_count(cutoffs.size(), ncols, name, "cutoffs");
+  for (size_t i = 0; i < cutoffs.size(); ++i) {
+    TORCH_CHECK(cutoffs[i].numel() <= GRADE_MAX_CELLS - 1, name, ": column ", i, " has ",
+                cutoffs[i].numel(), " cutoffs, at most ", GRADE_MAX_CELLS - 1, " fit");
+    auto cc = cutoffs[i].to(torch::kFloat64).cpu().contiguous();
+    const double *c = cc.data_ptr<double>();
+    for (int64_t j = 0; j < cc.numel(); ++j)
+      TORCH_CHECK(c[j] == c[j] && (j == 0 || c[j] > c[j - 1]), name, ": cutoffs of column ", i,
+                  " must be strictly ascending without NaN");
+  }
+}
+
+}  // namespace
+
+// K24 counting pass: int64 [ncols, max_ncut + 2] local counts in the
+// original column order, slot 0 nulls, slot 1 + j cell j = #{c : c < x}.
+torch::Tensor grade_counts(std::vector<torch::Tensor> cols, std::vector<torch::Tensor> cutoffs) {
+  ColumnBatch all = gather_columns(cols, "grade_counts", F32 | F64);
+  check_grade_cutoffs(cutoffs, cols.size(), all.name);
+  auto device = all.device;
+  int64_t stride = 2;
+  for (auto &c : cutoffs) stride = std::max<int64_t>(stride, c.numel() + 2);
+  auto counts = torch::zeros({all.ncols(), stride}, on(device, torch::kInt64));
+  for (auto &b : split_by_dtype(all)) {
+    CutoffTable ct = cutoff_table(cutoffs, b.idx);
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto doff = upload(ct.offs, device);
+    auto dflat = upload(ct.flat, device);
+    auto dclen = upload(ct.lens, device);
+    std::vector<int64_t> coffs;
+    for (int64_t i : b.idx) coffs.push_back(i * stride);
+    auto dcoff = upload(coffs, device);
+    check_hip(anovos_grade_counts(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                                  dflat.data_ptr<double>(), doff.data_ptr<int64_t>(),
+                                  dclen.data_ptr<int>(), ct.max_ncut, nchunks, b.dtype,
+                                  (uint64_t *)counts.data_ptr<int64_t>(),
+                                  dcoff.data_ptr<int64_t>(), current_stream()),
+              "anovos_grade_counts");
+  }
+  return counts;
+}
+
+// K24 transform pass: f32 tables[col][cell(x)], null_grade for NaN, into
+// `outs` when given (dense f32 tensors of the columns' lengths on their
+// device) or into new tensors.
+std::vector<torch::Tensor> grade_apply(std::vector<torch::Tensor> cols,
+                                       std::vector<torch::Tensor> cutoffs,
+                                       std::vector<torch::Tensor> tables, double null_grade,
+                                       std::optional<std::vector<torch::Tensor>> outs_in) {
+  ColumnBatch all = gather_columns(cols, "grade_apply", F32 | F64);
+  check_grade_cutoffs(cutoffs, cols.size(), all.name);
+  check_count(tables.size(), cols.size(), all.name, "tables");
+  for (size_t i = 0; i < tables.size(); ++i)
+    TORCH_CHECK(tables[i].numel() == cutoffs[i].numel() + 1, all.name, ": table of column ", i,
+                " has ", tables[i].numel(), " entries, expected ", cutoffs[i].numel() + 1);
+  auto device = all.device;
+  std::vector<torch::Tensor> outs;
+  if (outs_in.has_value()) {
+    outs = *outs_in;
+    check_count(outs.size(), cols.size(), all.name, "outs");
+    for (size_t i = 0; i < outs.size(); ++i)
+      check_dense_on_device(outs[i], all, "outs", torch::kFloat32, cols[i].numel());
+  } else {
+    for (auto &t : cols) outs.push_back(torch::empty(t.sizes(), on(device, torch::kFloat32)));
+  }
+  for (auto &b : split_by_dtype(all)) {
+    CutoffTable ct = cutoff_table(cutoffs, b.idx);
+    std::vector<float> tflat;
+    std::vector<int64_t> toffs;
+    for (int64_t i : b.idx) {
+      auto tc = tables[i].to(torch::kFloat32).cpu().contiguous();
+      toffs.push_back((int64_t)tflat.size());
+      tflat.insert(tflat.end(), tc.data_ptr<float>(), tc.data_ptr<float>() + tc.numel());
+    }
+    int nchunks = pick_chunks(b.maxn, b.ncols());
+    auto dptr = upload(b.ptrs, device);
+    auto dlen = upload(b.lens, device);
+    auto dout = upload(out_ptrs(outs, b), device);
+    auto doff = upload(ct.offs, device);
+    auto dflat = upload(ct.flat, device);
+    auto dclen = upload(ct.lens, device);
+    auto dtoff = upload(toffs, device);
+    auto dtflat = upload(tflat, device);
+    check_hip(anovos_grade_apply(ptr_table<const void>(dptr), dlen.data_ptr<int64_t>(), b.ncols(),
+                                 dflat.data_ptr<double>(), doff.data_ptr<int64_t>(),
+                                 dclen.data_ptr<int>(), dtflat.data_ptr<float>(),
+                                 dtoff.data_ptr<int64_t>(), (float)null_grade, ct.max_ncut,
+                                 nchunks, b.dtype, ptr_table<float>(dout), current_stream()),
+              "anovos_grade_apply");
+  }
+  return outs;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("code_counts_multi", &code_counts_multi, "fused multi-column code counts + null slot (K5)",
+  m.def("grade_counts", &grade_counts, "rows per grid cell of each column, read-only (K24)");
+  m.def("grade_apply", &grade_apply, "per-cell grade lookup to f32 columns (K24)",
+        py::arg("cols"), py::arg("cutoffs"), py::arg("tables"), py::arg("null_grade"),
+        py::arg("outs") = py::none());
+  m.attr("GRADE_MAX_CELLS") = GRADE_MAX_CELLS;
+  m.def("code_counts_multi",&code_counts_multi, "fused multi-column code counts + null slot (K5)",
         py::arg("cols"), py::arg("sizes"), py::arg("null_masks") = false);
   m.def("pair_code_counts", &pair_code_counts, "contingency tables of code-column pairs (K22)");
   m.def("pair_code_counts_plan", &pair_code_counts_plan,

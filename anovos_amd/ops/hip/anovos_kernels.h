@@ -2,7 +2,7 @@
 //
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
-// grouped_moments.hip):
+// grouped_moments.hip, grades.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -44,6 +44,9 @@ constexpr int RB_MAXB = 16;
 constexpr int LABEL_MAX_SLOTS = 8192;
 // K6 with counts: cutoffs per column (doubles + uint32 counters in LDS)
 constexpr int BKT_COUNTS_MAX_NCUT = 4096;
+// K24: cells of a column's rank grid (at most GRADE_MAX_CELLS - 1 cutoffs;
+// cutoffs, counters and the grade table of one column in LDS)
+constexpr int GRADE_MAX_CELLS = 4096;
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -158,4 +161,14 @@ int anovos_grouped_moments(const int32_t *const *codes, const void *const *vals,
                            const double *shifts, const int64_t *items, int nitems,
                            int64_t n, int64_t per, int nchunks, int cells, int dtype,
                            double *partials, double *out, hipStream_t stream);
+// grades.hip
+int anovos_grade_counts(const void *const *cols, const int64_t *lens, int ncols,
+                        const double *cutflat, const int64_t *cutoff_off,
+                        const int *cutoff_len, int max_ncut, int nchunks, int dtype,
+                        uint64_t *counts, const int64_t *count_off, hipStream_t stream);
+int anovos_grade_apply(const void *const *cols, const int64_t *lens, int ncols,
+                       const double *cutflat, const int64_t *cutoff_off,
+                       const int *cutoff_len, const float *tabflat, const int64_t *tab_off,
+                       float null_grade, int max_ncut, int nchunks, int dtype,
+                       float *const *outs, hipStream_t stream);
 }

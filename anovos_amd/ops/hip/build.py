@@ -28,6 +28,7 @@ def build(verbose: bool = True) -> str:
             os.path.join(HERE, "corr_mfma.hip"),
             os.path.join(HERE, "pair_counts.hip"),
             os.path.join(HERE, "grouped_moments.hip"),
+            os.path.join(HERE, "grades.hip"),
         ],
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],
