@@ -116,6 +116,20 @@ def compute_bin_cutoffs(ctx, idf, list_of_cols, method_type, bin_size):
     return list_of_cols, bin_cutoffs
 
 
+def _device_bin_cutoffs(idf, list_of_cols, method_type, bin_size):
+    """compute_bin_cutoffs for a consumer on the device: the equal-frequency
+    cutoffs of `list_of_cols` as an fp64 [ncols, bin_size - 1] device tensor,
+    bit for bit what compute_bin_cutoffs returns, without a sync. None when
+    the method is another one or a column is not served from cached device
+    histograms (ops/histogram.device_quantile_matrix); the caller then
+    takes compute_bin_cutoffs."""
+    if method_type != "equal_frequency":
+        return None
+    pctile_width = 1 / bin_size
+    probs = [j * pctile_width for j in range(1, bin_size)]
+    return hist_ops.device_quantile_matrix(idf, list_of_cols, probs, rel_err=0.01)
+
+
 def attribute_binning(
     ctx,
     idf,

@@ -1055,12 +1055,29 @@ torch::Tensor label_counts_multi(std::vector<torch::Tensor> cols, torch::Tensor 
 // K6+K9 fused: bucketize against per-column cutoffs + label-conditioned
 // counts in one read of the RAW numeric columns (no binned
 // materialization). Returns flat int64: per column [slots] totals then
-// [slots] events at offsets in the ORIGINAL column order.
-torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
-                                     std::vector<torch::Tensor> cutoffs, torch::Tensor label,
-                                     std::vector<int64_t> sizes) {
-  ColumnBatch all = gather_columns(cols, "bucketize_label_counts", F32 | F64, /*equal_len=*/true);
-  check_count(cutoffs.size(), cols.size(), all.name, "cutoffs");
+// [slots] events at offsets in the ORIGINAL column order. The cutoffs are
+// host lists (one tensor per column, flattened and uploaded), or with
+// cut_matrix one contiguous fp64 [ncols, ncut] device tensor that the
+// kernel reads where it lies: nothing is copied and nothing waits.
+namespace {
+torch::Tensor bucketize_label_counts_body(const std::vector<torch::Tensor> &cols,
+                                          const std::vector<torch::Tensor> *cutoffs,
+                                          const torch::Tensor *cut_matrix,
+                                          const torch::Tensor &label,
+                                          const std::vector<int64_t> &sizes, const char *name) {
+  ColumnBatch all = gather_columns(cols, name, F32 | F64, /*equal_len=*/true);
+  int64_t ncut = 0;
+  if (cutoffs) {
+    check_count(cutoffs->size(), cols.size(), all.name, "cutoffs");
+  } else {
+    TORCH_CHECK(cut_matrix->dim() == 2 && cut_matrix->size(0) == (int64_t)cols.size() &&
+                    cut_matrix->size(1) >= 1 && cut_matrix->size(1) <= LABEL_MAX_SLOTS,
+                all.name, ": cut_matrix must be [ncols, ncut] with 1 <= ncut <= ", LABEL_MAX_SLOTS);
+    TORCH_CHECK(cut_matrix->device() == all.device && cut_matrix->is_contiguous() &&
+                    cut_matrix->scalar_type() == torch::kFloat64,
+                all.name, ": cut_matrix must be a contiguous float64 tensor on the columns' device");
+    ncut = cut_matrix->size(1);
+  }
   check_count(sizes.size(), cols.size(), all.name, "sizes");
   check_dense_on_device(label, all, "label", torch::kUInt8, all.maxn);
   auto device = all.device;
@@ -1073,7 +1090,17 @@ torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
   }
   auto out = torch::zeros({total}, on(device, torch::kInt64));
   for (auto &b : split_by_dtype(all)) {
-    CutoffTable ct = cutoff_table(cutoffs, b.idx);
+    CutoffTable ct;
+    torch::Tensor dflat;
+    if (cutoffs) {
+      ct = cutoff_table(*cutoffs, b.idx);
+      dflat = upload(ct.flat, device);
+    } else {
+      for (int64_t i : b.idx) ct.offs.push_back(i * ncut);
+      ct.lens.assign(b.idx.size(), (int)ncut);
+      ct.max_ncut = (int)ncut;
+      dflat = *cut_matrix;
+    }
     auto sz = pick(sizes, b.idx);
     int max_slots = (int)std::max<int64_t>(1, *std::max_element(sz.begin(), sz.end()));
     int nchunks = pick_chunks(b.maxn, b.ncols());
@@ -1081,7 +1108,6 @@ torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
     auto dlen = upload(b.lens, device);
     auto doff = upload(pick(out_offs, b.idx), device);
     auto dcoff = upload(ct.offs, device);
-    auto dflat = upload(ct.flat, device);
     auto dclen = upload(ct.lens, device);
     auto dsz = upload(std::vector<int>(sz.begin(), sz.end()), device);
     check_hip(anovos_bucketize_label_counts(
@@ -1092,6 +1118,85 @@ torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
               "anovos_bucketize_label_counts");
   }
   return out;
+}
+
+// One per-column fp64 parameter of a quantile query: dense, on `dev`.
+const double *query_param(const torch::Tensor &t, int64_t ncols, const torch::Device &dev,
+                          const char *name, const char *what) {
+  TORCH_CHECK(t.device() == dev && t.is_contiguous() && t.scalar_type() == torch::kFloat64 &&
+                  t.numel() == ncols,
+              name, ": ", what, " must be a contiguous float64 tensor of ", ncols,
+              " entries on the histogram's device");
+  return t.data_ptr<double>();
+}
+
+void check_query_matrix(const torch::Tensor &h, const std::vector<double> &probs, const char *name) {
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() && h.scalar_type() == torch::kInt64,
+              name, ": expected a contiguous int64 [ncols, nbins] device tensor");
+  TORCH_CHECK(h.size(0) >= 1 && h.size(1) >= 1 && h.size(1) <= QQ_MAX_BINS, name,
+              ": need at least one column and 1 .. ", QQ_MAX_BINS, " bins");
+  TORCH_CHECK(!probs.empty(), name, ": no probabilities");
+}
+}  // namespace
+
+torch::Tensor bucketize_label_counts(std::vector<torch::Tensor> cols,
+                                     std::vector<torch::Tensor> cutoffs, torch::Tensor label,
+                                     std::vector<int64_t> sizes) {
+  return bucketize_label_counts_body(cols, &cutoffs, nullptr, label, sizes,
+                                     "bucketize_label_counts");
+}
+
+torch::Tensor bucketize_label_counts_dev(std::vector<torch::Tensor> cols, torch::Tensor cut_matrix,
+                                         torch::Tensor label, std::vector<int64_t> sizes) {
+  return bucketize_label_counts_body(cols, nullptr, &cut_matrix, label, sizes,
+                                     "bucketize_label_counts_dev");
+}
+
+// K3q: quantiles of [ncols, nbins] pass-1 histograms that are on the device.
+// Returns (values f64 [ncols, P], refine flags u8 [ncols, P], largest bin
+// count int64 [ncols]), all left on the device.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> hist_quantile_query(
+    torch::Tensor hist, torch::Tensor lo, torch::Tensor hi, torch::Tensor n,
+    std::vector<double> probs, double rel_err) {
+  const char *name = "hist_quantile_query";
+  check_query_matrix(hist, probs, name);
+  const int64_t ncols = hist.size(0), P = (int64_t)probs.size();
+  auto dev = hist.device();
+  const double *plo = query_param(lo, ncols, dev, name, "lo");
+  const double *phi = query_param(hi, ncols, dev, name, "hi");
+  const double *pn = query_param(n, ncols, dev, name, "n");
+  auto vals = torch::empty({ncols, P}, on(dev, torch::kFloat64));
+  auto flags = torch::empty({ncols, P}, on(dev, torch::kUInt8));
+  auto maxbin = torch::empty({ncols}, on(dev, torch::kInt64));
+  auto dprobs = upload(probs, dev);
+  check_hip(anovos_hist_quantile_query((const uint64_t *)hist.data_ptr<int64_t>(), plo, phi, pn,
+                                       dprobs.data_ptr<double>(), rel_err, (int)ncols,
+                                       (int)hist.size(1), (int)P, vals.data_ptr<double>(),
+                                       flags.data_ptr<uint8_t>(), maxbin.data_ptr<int64_t>(),
+                                       current_stream()),
+            "anovos_hist_quantile_query");
+  return {vals, flags, maxbin};
+}
+
+// K3q, dense integer counts: column c holds the counts of cmin[c] + 0 ..
+// R[c] - 1 in the first R[c] entries of its row. Returns f64 [ncols, P].
+torch::Tensor inthist_quantile_query(torch::Tensor counts, torch::Tensor cmin, torch::Tensor n,
+                                     torch::Tensor R, std::vector<double> probs, double rel_err) {
+  const char *name = "inthist_quantile_query";
+  check_query_matrix(counts, probs, name);
+  const int64_t ncols = counts.size(0), P = (int64_t)probs.size();
+  auto dev = counts.device();
+  const double *pmin = query_param(cmin, ncols, dev, name, "cmin");
+  const double *pn = query_param(n, ncols, dev, name, "n");
+  const double *pR = query_param(R, ncols, dev, name, "R");
+  auto vals = torch::empty({ncols, P}, on(dev, torch::kFloat64));
+  auto dprobs = upload(probs, dev);
+  check_hip(anovos_inthist_quantile_query((const uint64_t *)counts.data_ptr<int64_t>(),
+                                          (int)counts.size(1), pmin, pn, pR,
+                                          dprobs.data_ptr<double>(), rel_err, (int)ncols, (int)P,
+                                          vals.data_ptr<double>(), current_stream()),
+            "anovos_inthist_quantile_query");
+  return vals;
 }
 
 // K10/K11 fused: outlier counts + clamp/null treatment in one launch.
@@ -1246,6 +1351,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("outlier_clamp_columns", &outlier_clamp_columns, "fused outlier count/clamp (K10/K11)");
   m.def("label_counts_multi", &label_counts_multi, "fused multi-column label-conditioned histograms (K9)");
   m.def("bucketize_label_counts", &bucketize_label_counts, "fused bucketize + label counts, no binned materialization (K6+K9)");
+  m.def("bucketize_label_counts_dev", &bucketize_label_counts_dev,
+        "bucketize_label_counts with the cutoffs as a device [ncols, ncut] matrix (K6+K9)");
+  m.def("hist_quantile_query", &hist_quantile_query, "quantiles of device-resident histograms (K3q)");
+  m.def("inthist_quantile_query", &inthist_quantile_query,
+        "exact quantiles of device-resident dense integer counts (K3q)");
   m.def("moments_hll", &moments_hll, "fused moments + HLL registers (K1/K2+K4)",
         py::arg("cols"), py::arg("p"), py::arg("shifts") = std::vector<double>(),
         py::arg("null_masks") = false);

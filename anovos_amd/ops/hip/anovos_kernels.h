@@ -47,6 +47,9 @@ constexpr int BKT_COUNTS_MAX_NCUT = 4096;
 // K24: cells of a column's rank grid (at most GRADE_MAX_CELLS - 1 cutoffs;
 // cutoffs, counters and the grade table of one column in LDS)
 constexpr int GRADE_MAX_CELLS = 4096;
+// K3q: bins (or dense integer counts) of one column whose CDF the
+// quantile-query kernels hold in LDS as uint64
+constexpr int QQ_MAX_BINS = 4096;
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -142,6 +145,19 @@ int anovos_label_counts_multi(const void *const *cols, const uint8_t *label,
                               const int *sizes, const int *dtypes, int ncols,
                               int max_slots, int nchunks, uint64_t *out,
                               hipStream_t stream);
+// K3q: quantile queries on device-resident histograms, one block per
+// column. hist is [ncols, nbins] (nbins <= QQ_MAX_BINS); lo / hi / n are
+// per column, probs has P entries; vals and flags are [ncols, P], maxbin
+// [ncols]. The dense-integer form reads the first R[c] (given as fp64) of
+// the `rows` counts of column c.
+int anovos_hist_quantile_query(const uint64_t *hist, const double *lo, const double *hi,
+                               const double *n, const double *probs, double rel_err,
+                               int ncols, int nbins, int P, double *vals, uint8_t *flags,
+                               int64_t *maxbin, hipStream_t stream);
+int anovos_inthist_quantile_query(const uint64_t *counts, int rows, const double *cmin,
+                                  const double *n, const double *R, const double *probs,
+                                  double rel_err, int ncols, int P, double *vals,
+                                  hipStream_t stream);
 // corr_mfma.hip
 int anovos_centered_gram(const void *const *cols, int64_t n, int k,
                          const float *means, const int *pair_i,

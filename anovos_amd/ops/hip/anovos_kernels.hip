@@ -2238,3 +2238,159 @@ extern "C" int anovos_bucketize_label_counts(
 #undef BKT_LABEL_F32
   return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------
+// K3q: quantile queries on histograms that stay on the device.
+// ------------------------------------------------------------------
+// One block per column. The block builds the column's inclusive CDF in LDS
+// (exact integer sums; the host sums the same counts in fp64, which is exact
+// below 2^53) and one thread per probability then does what
+// ops/histogram.host_quantile_query does for a bracket that needs no
+// refinement. The values must carry the host's bits, so every fp64 step is
+// written in the host's order and contraction is off: an fma in
+// lo + b * w or in the interpolation would change the last bit. min / max
+// are spelled as the comparisons Python's min() / max() make.
+
+// Inclusive prefix sum of h[0 .. nb) into cdf; returns the largest count.
+// Thread t sums the contiguous run [t * per, (t + 1) * per) and then adds
+// the totals of the runs before it.
+DEV_INLINE uint64_t qq_prefix(const uint64_t *__restrict__ h, int nb, uint64_t *cdf,
+                              uint64_t *part, uint64_t *pmax) {
+  const int per = (nb + THREADS - 1) / THREADS;
+  const int s = min(nb, (int)threadIdx.x * per);
+  const int e = min(nb, s + per);
+  uint64_t run = 0, mx = 0;
+  for (int i = s; i < e; ++i) {
+    const uint64_t c = h[i];
+    run += c;
+    mx = c > mx ? c : mx;
+    cdf[i] = run;
+  }
+  part[threadIdx.x] = run;
+  pmax[threadIdx.x] = mx;
+  __syncthreads();
+  uint64_t before = 0, allmax = 0;
+  for (int t = 0; t < THREADS; ++t) {
+    before += t < (int)threadIdx.x ? part[t] : 0;
+    allmax = pmax[t] > allmax ? pmax[t] : allmax;
+  }
+  for (int i = s; i < e; ++i) cdf[i] += before;
+  __syncthreads();
+  return allmax;
+}
+
+// #{i < nb : cdf[i] < t}: cdf does not decrease, so a binary search.
+DEV_INLINE int qq_count_below(const uint64_t *cdf, int nb, double t) {
+  int lo = 0, len = nb;
+  while (len > 0) {
+    const int half = len >> 1;
+    const bool lt = (double)cdf[lo + half] < t;
+    lo = lt ? lo + half + 1 : lo;
+    len = lt ? len - half - 1 : half;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(THREADS) void hist_quantile_query_kernel(
+    const uint64_t *__restrict__ hist, const double *__restrict__ lo,
+    const double *__restrict__ hi, const double *__restrict__ n,
+    const double *__restrict__ probs, double rel_err, int nbins, int P,
+    double *__restrict__ vals, uint8_t *__restrict__ flags, int64_t *__restrict__ maxbin) {
+#pragma clang fp contract(off)
+  __shared__ uint64_t cdf[QQ_MAX_BINS];
+  __shared__ uint64_t part[THREADS];
+  __shared__ uint64_t pmax[THREADS];
+  const int col = blockIdx.x;
+  const uint64_t mx = qq_prefix(hist + (size_t)col * nbins, nbins, cdf, part, pmax);
+  if (threadIdx.x == 0) maxbin[col] = (int64_t)mx;
+  const double l = lo[col], h = hi[col], nn = n[col];
+  for (int j = threadIdx.x; j < P; j += THREADS) {
+    double v;
+    bool over = false;
+    if (!(nn > 0.0) || l != l) {
+      v = __longlong_as_double(0x7ff8000000000000LL);
+    } else if (h <= l) {
+      v = l;
+    } else {
+      const double target = probs[j] * (nn - 1.0);
+      const int a = qq_count_below(cdf, nbins, target + 0.5);
+      const int b = a < nbins - 1 ? a : nbins - 1;
+      const uint64_t cb = b > 0 ? cdf[b - 1] : 0;
+      const double below = (double)cb;
+      const double cnt = (double)(cdf[b] - cb);
+      const double w = (h - l) / (double)nbins;
+      const double bl = l + (double)b * w;
+      const double bh = l + (double)(b + 1) * w;
+      if (cnt <= 1.0 || bh <= bl) {
+        v = bl;
+      } else {
+        const double den = cnt - 1.0;
+        double frac = (target - below) / (1e-9 > den ? 1e-9 : den);
+        frac = 0.0 > frac ? 0.0 : frac;
+        frac = 1.0 < frac ? 1.0 : frac;
+        v = bl + frac * (bh - bl);
+      }
+      if (b == nbins - 1) v = h < v ? h : v;
+      const double nmax = 1.0 > nn ? 1.0 : nn;
+      over = cnt > rel_err * 0.5 * nmax;
+    }
+    vals[(size_t)col * P + j] = v;
+    flags[(size_t)col * P + j] = over ? 1 : 0;
+  }
+}
+
+// Dense integer counts (bin width exactly 1): the exact rule of
+// ops/histogram._exact_integral_quantiles. rows is the row stride of counts;
+// column c uses its first R[c] entries.
+__global__ __launch_bounds__(THREADS) void inthist_quantile_query_kernel(
+    const uint64_t *__restrict__ counts, int rows, const double *__restrict__ cmin,
+    const double *__restrict__ n, const double *__restrict__ Rf,
+    const double *__restrict__ probs, double rel_err, int P, double *__restrict__ vals) {
+#pragma clang fp contract(off)
+  __shared__ uint64_t cdf[QQ_MAX_BINS];
+  __shared__ uint64_t part[THREADS];
+  __shared__ uint64_t pmax[THREADS];
+  const int col = blockIdx.x;
+  int R = (int)Rf[col];
+  R = R < 1 ? 1 : (R > rows ? rows : R);
+  qq_prefix(counts + (size_t)col * rows, R, cdf, part, pmax);
+  const double nn = n[col], c0 = cmin[col];
+  for (int j = threadIdx.x; j < P; j += THREADS) {
+    const double p = probs[j];
+    double r;
+    if (p <= rel_err) {
+      r = 1.0;
+    } else if (p >= 1.0 - rel_err) {
+      r = nn;
+    } else {
+      r = ceil(p * nn);
+      r = 1.0 > r ? 1.0 : r;
+      r = nn < r ? nn : r;
+    }
+    const int a = qq_count_below(cdf, R, r);
+    const int b = a < R - 1 ? a : R - 1;
+    vals[(size_t)col * P + j] = c0 + (double)b;
+  }
+}
+
+extern "C" int anovos_hist_quantile_query(const uint64_t *hist, const double *lo,
+                                          const double *hi, const double *n,
+                                          const double *probs, double rel_err, int ncols,
+                                          int nbins, int P, double *vals, uint8_t *flags,
+                                          int64_t *maxbin, hipStream_t stream) {
+  if (nbins < 1 || nbins > QQ_MAX_BINS || P < 1 || ncols < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(hist_quantile_query_kernel, dim3(ncols), dim3(THREADS), 0, stream, hist,
+                     lo, hi, n, probs, rel_err, nbins, P, vals, flags, maxbin);
+  return (int)hipGetLastError();
+}
+
+extern "C" int anovos_inthist_quantile_query(const uint64_t *counts, int rows,
+                                             const double *cmin, const double *n,
+                                             const double *R, const double *probs,
+                                             double rel_err, int ncols, int P, double *vals,
+                                             hipStream_t stream) {
+  if (rows < 1 || rows > QQ_MAX_BINS || P < 1 || ncols < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(inthist_quantile_query_kernel, dim3(ncols), dim3(THREADS), 0, stream,
+                     counts, rows, cmin, n, R, probs, rel_err, P, vals);
+  return (int)hipGetLastError();
+}

@@ -17,6 +17,7 @@ that stays unresolved, are sorted.
 
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -36,6 +37,108 @@ MAX_REFINE_PASSES = 8
 # distinct doubles. An f32 ulp is 2^29 f64 ulps, so f32 values still
 # separate long before this.
 _MIN_SPLIT_ULPS = 4 * 2048
+# Bins of one histogram the device quantile query (K3q) holds in LDS
+# (QQ_MAX_BINS of ops/hip/anovos_kernels.h)
+QQ_MAX_BINS = 4096
+
+
+def device_quantiles_enabled() -> bool:
+    """ANOVOS_DEVICE_QUANTILES=0 turns the device quantile queries (K3q) off:
+    pass-1 histograms come back to the host and every bracket is located
+    there, as on the CPU (A/B runs, equality tests)."""
+    return os.environ.get("ANOVOS_DEVICE_QUANTILES", "1") != "0"
+
+
+def _on_hip(idf, cols) -> bool:
+    t = idf.col(cols[0]).data
+    return t.device.type == "cuda" and backend.use_hip(t)
+
+
+def _pass1_brackets(hist_np, lows, highs, ns, probs):
+    """Bracket per (col, prob) from fp64 pass-1 histograms [K, nbins] over
+    [lows_i, highs_i] with ns_i non-null values: the bin that contains the
+    target rank. Returns (constant, active, brackets, top): {col: value} for
+    columns whose range is a single point, the indices of the columns with
+    brackets, {(col, prob index): (bl, bh, off, cnt)}, and the set of
+    brackets on the last bin. Columns in neither have no values (NaN)."""
+    import numpy as np
+
+    nbins = hist_np.shape[1]
+    cdf = np.cumsum(hist_np, axis=1)
+    # fully vectorized over the (col x prob) grid (the per-pair python loop
+    # cost ~5 ms/step at 150x9)
+    brackets = {}
+    top = set()  # brackets on the last pass-1 bin
+    probs_np = np.asarray(probs)
+    P = len(probs)
+    lows = np.asarray(lows).astype(np.float64)
+    valid = (ns > 0) & (lows == lows)
+    degenerate = valid & (highs <= lows)
+    constant = {int(i): float(lows[i]) for i in np.nonzero(degenerate)[0]}
+    active = np.nonzero(valid & ~degenerate)[0]
+    if active.size:
+        w = (highs[active] - lows[active]) / nbins  # [A]
+        targets = probs_np[None, :] * (ns[active, None] - 1)  # [A,P]
+        # vectorized per-row searchsorted: count of cdf entries < target
+        cdf_a = cdf[active]  # [A,nbins]
+        bs = np.minimum((cdf_a[:, :, None] < (targets + 0.5)[:, None, :]).sum(axis=1), nbins - 1)  # [A,P]
+        rows = np.arange(active.size)[:, None]
+        belows = np.where(bs > 0, cdf_a[rows, np.maximum(bs - 1, 0)], 0.0)
+        cnts = hist_np[active][rows, bs]
+        for a, i in enumerate(active):
+            l = lows[i]
+            wa = w[a]
+            for j in range(P):
+                b = int(bs[a, j])
+                brackets[(int(i), j)] = (l + b * wa, l + (b + 1) * wa, float(targets[a, j] - belows[a, j]), float(cnts[a, j]))
+        top = {(int(active[a]), int(j)) for a, j in zip(*np.nonzero(bs == nbins - 1))}
+    return constant, active, brackets, top
+
+
+def _bracket_values(brackets, point, top, highs):
+    """{(col, prob index): value} of final brackets (bl, bh, off, cnt), of
+    the data values `point` that spike brackets resolved to, and the cap of
+    the last pass-1 bin at the column maximum."""
+    out = {}
+    for k, (bl, bh, off, cnt) in brackets.items():
+        if cnt <= 1 or bh <= bl:
+            out[k] = bl
+        else:
+            # interpolate inside the (now tiny) bracket by rank fraction
+            frac = min(max(off / max(cnt - 1, 1e-9), 0.0), 1.0) if cnt > 1 else 0.0
+            out[k] = bl + frac * (bh - bl)
+    for k, v in point.items():
+        out[k] = v
+    for k in top:
+        # the last pass-1 bin's upper bound may round to just above the maximum
+        out[k] = min(out[k], float(highs[k[0]]))
+    return out
+
+
+def host_quantile_query(hist, lo, hi, n, probs, rel_err):
+    """Quantiles from pass-1 histograms alone, on the host: what
+    approx_quantiles returns for brackets that need no refinement. hist is
+    [K, nbins] counts, lo / hi / n are per column. Returns fp64 values
+    [K, P], bool flags [K, P] (the bracket holds more than rel_err / 2 of
+    the rank mass, so approx_quantiles would refine it) and the largest bin
+    count [K]. The CPU path, and the reference of the device query (K3q)."""
+    import numpy as np
+
+    hist_np = np.asarray(hist).astype(np.float64)
+    lows = np.asarray(lo, dtype=np.float64)
+    highs = np.asarray(hi, dtype=np.float64)
+    ns = np.asarray(n, dtype=np.float64)
+    K, P = hist_np.shape[0], len(probs)
+    vals = np.full((K, P), float("nan"))
+    flags = np.zeros((K, P), dtype=bool)
+    constant, active, brackets, top = _pass1_brackets(hist_np, lows, highs, ns, list(probs))
+    for i, v in constant.items():
+        vals[i, :] = v
+    for (i, j), v in _bracket_values(brackets, {}, top, highs).items():
+        vals[i, j] = v
+    for (i, j), v in brackets.items():
+        flags[i, j] = v[3] > rel_err * 0.5 * max(ns[i], 1.0)
+    return vals, flags, hist_np.max(axis=1)
 
 
 def _splittable(bracket):
@@ -128,16 +231,30 @@ def _exact_integral_quantiles(idf, cols, probs, moments, rel_err=0.0):
     R = {c: int(moments[c].max - moments[c].min) + 1 for c in cols}
     # a column whose dense counts are already cached (an earlier call with
     # other probabilities) is not read again
-    cold = [c for c in cols if ("inthist",) not in idf.col(c).cache]
+    use_dev = device_quantiles_enabled() and _on_hip(idf, cols)
+    dkey = ("inthist_dev",)
+    cold = [c for c in cols if ("inthist",) not in idf.col(c).cache or (use_dev and dkey not in idf.col(c).cache)]
     if cold:
         M = max(R[c] for c in cold)
         lo = torch.tensor([moments[c].min - 0.5 for c in cold], dtype=torch.float64)
         hi = torch.tensor([moments[c].min - 0.5 + M for c in cold], dtype=torch.float64)
-        h = global_histograms([idf.col(c).data for c in cold], lo, hi, M).cpu().numpy()
+        hd = global_histograms([idf.col(c).data for c in cold], lo, hi, M)
+        if use_dev:
+            # the counts stay on the device as well, with (min, n, R) per column
+            meta = torch.tensor([[moments[c].min for c in cold], [float(int(moments[c].n)) for c in cold],
+                                 [float(R[c]) for c in cold]], dtype=torch.float64).to(hd.device)
+            for i, c in enumerate(cold):
+                idf.col(c).cache[dkey] = (hd, meta, i)
+    # K3q answers on the device; launched before the counts are fetched
+    vals_d = _device_integral_query(idf, cols, probs, rel_err) if use_dev else None
+    if cold:
+        h = hd.cpu().numpy()
         for i, c in enumerate(cold):
             # the dense per-integer counts serve discrete_modes too — one
             # frame read covers exact quantiles AND exact modes
             idf.col(c).cache[("inthist",)] = (h[i][: R[c]].copy(), float(moments[c].min))
+    if vals_d is not None:
+        return dict(zip(cols, vals_d.cpu().tolist()))
     out = {}
     for c in cols:
         n = int(moments[c].n)
@@ -273,14 +390,153 @@ def approx_quantiles(
                                moments=moments, rel_err=rel_err)
         out.update(dense)
         return {c: out[c] for c in cols}
+    if device_quantiles_enabled() and nbins <= QQ_MAX_BINS and _on_hip(idf, cols):
+        # K3q: the histograms stay on the device and are queried there; only
+        # the columns with a bracket above the refinement threshold take the
+        # host path below
+        H, meta = _device_histograms(idf, cols, nbins, moments)
+        dv, df, dm = backend.hip_ext().hist_quantile_query(H, meta[0], meta[1], meta[2], probs_l, float(rel_err))
+        vals, flagged, maxbin = dv.cpu().tolist(), df.cpu().numpy().any(axis=1), dm.cpu().tolist()
+        host_cols = []
+        for i, c in enumerate(cols):
+            idf.col(c).cache[("hist_maxbin", nbins)] = maxbin[i]
+            if flagged[i]:
+                host_cols.append(c)
+            else:
+                for j, p in enumerate(probs_l):
+                    idf.col(c).cache[("q", p)] = vals[i][j]
+        out = _host_bracket_quantiles(idf, cols, probs_l, nbins, refine, moments, rel_err, only=host_cols) if host_cols else {}
+        return {c: out[c] if c in out else vals[i] for i, c in enumerate(cols)}
+    return _host_bracket_quantiles(idf, cols, probs_l, nbins, refine, moments, rel_err)
+
+
+def _device_histograms(idf, cols, nbins, moments):
+    """The all-reduced pass-1 histograms of `cols` as one int64
+    [ncols, nbins] device tensor, with their fp64 [3, ncols] (lo, hi, n).
+    A column's cache holds (matrix, parameters, row) of the call that read
+    it; columns not read yet are read here, in one launch."""
+    dkey = ("hist_dev", nbins)
+    todo = [c for c in cols if dkey not in idf.col(c).cache]
+    if todo:
+        lo = torch.tensor([moments[c].min for c in todo], dtype=torch.float64)
+        hi = torch.tensor([moments[c].max for c in todo], dtype=torch.float64)
+        h = global_histograms([idf.col(c).data for c in todo], lo, hi, nbins)
+        n = torch.tensor([moments[c].n for c in todo], dtype=torch.float64)
+        meta = torch.stack([lo, hi, n]).to(h.device)
+        for k, c in enumerate(todo):
+            idf.col(c).cache[dkey] = (h, meta, k)
+    return _gather_cached_rows([idf.col(c).cache[dkey] for c in cols])
+
+
+def _gather_cached_rows(entries):
+    """(matrix, parameters) of cached (matrix, parameters, row) entries: the
+    cached tensors themselves when the entries are all of one call, in its
+    order; otherwise the rows are copied together."""
+    base, meta, _ = entries[0]
+    if all(e[0] is base for e in entries) and [e[2] for e in entries] == list(range(base.shape[0])):
+        return base, meta
+    if any(e[0].shape[1] != base.shape[1] for e in entries):
+        return None, None
+    return (torch.stack([e[0][e[2]] for e in entries]),
+            torch.stack([e[1][:, e[2]] for e in entries], dim=1).contiguous())
+
+
+def _device_integral_query(idf, cols, probs, rel_err):
+    """Exact quantiles of integral columns from their cached device counts
+    (K3q): fp64 [ncols, P] on the device, or None when the cached rows have
+    different widths."""
+    counts, meta = _gather_cached_rows([idf.col(c).cache[("inthist_dev",)] for c in cols])
+    if counts is None:
+        return None
+    return backend.hip_ext().inthist_quantile_query(counts, meta[0], meta[1], meta[2], list(probs), float(rel_err))
+
+
+def _is_dense_integral(m) -> bool:
+    return bool(m.n > 0 and m.integral and m.min == m.min and 0 < (m.max - m.min) < 4096)
+
+
+def device_quantile_matrix(idf, cols, probs, nbins: int = DEFAULT_BINS, rel_err: float = 1e-2):
+    """approx_quantiles(idf, cols, probs) as an fp64 [ncols, P] tensor that
+    never leaves the device, for a consumer that is a kernel: nothing is
+    synced. Possible when the device queries are on, every column's
+    histogram (or dense integer counts) is cached on the device and no
+    column can need refinement: its largest pass-1 bin is within the
+    refinement threshold. Returns None otherwise; the caller then takes
+    approx_quantiles. When every value is in the ("q", p) caches already
+    they are what is returned, as approx_quantiles does."""
+    import math as _math
+
+    from anovos_amd.ops import stats as stats_ops
+
+    probs = list(probs)
+    if not cols or not probs or not device_quantiles_enabled() or nbins > QQ_MAX_BINS or not _on_hip(idf, cols):
+        return None
+    moments = stats_ops.frame_moments(idf, cols)
+    if all(moments[c].n <= EXACT_N_THRESHOLD for c in cols):
+        return None
+    if all(all(("q", p) in idf.col(c).cache for p in probs) for c in cols):
+        held = [[idf.col(c).cache[("q", p)] for p in probs] for c in cols]
+        return torch.tensor(held, dtype=torch.float64).to(idf.col(cols[0]).data.device)
+    hist_cols, int_cols = [], []
+    for c in cols:
+        m, cache = moments[c], idf.col(c).cache
+        if _math.isinf(m.min) or _math.isinf(m.max):
+            return None
+        if _is_dense_integral(m):
+            # with every probability cached approx_quantiles no longer takes
+            # the column as integral
+            if ("inthist_dev",) not in cache or all(("q", p) in cache for p in probs):
+                return None
+            int_cols.append(c)
+        else:
+            mb = cache.get(("hist_maxbin", nbins))
+            if mb is None or ("hist_dev", nbins) not in cache:
+                return None
+            # only a column with values over a range has brackets to refine
+            ranged = m.n > 0 and m.min == m.min and not m.max <= m.min
+            if ranged and mb > rel_err * 0.5 * max(m.n, 1.0):
+                return None
+            hist_cols.append(c)
+    ext = backend.hip_ext()
+    parts = []
+    if hist_cols:
+        H, meta = _device_histograms(idf, hist_cols, nbins, moments)
+        parts.append(ext.hist_quantile_query(H, meta[0], meta[1], meta[2], probs, float(rel_err))[0])
+    if int_cols:
+        v = _device_integral_query(idf, int_cols, probs, rel_err)
+        if v is None:
+            return None
+        parts.append(v)
+    out = torch.cat(parts) if len(parts) > 1 else parts[0]
+    order = hist_cols + int_cols
+    if order != list(cols):
+        pos = {c: i for i, c in enumerate(order)}
+        out = out.index_select(0, torch.tensor([pos[c] for c in cols], dtype=torch.long).to(out.device))
+    return out.contiguous()
+
+
+def _host_bracket_quantiles(idf, cols, probs, nbins, refine, moments, rel_err, only=None):
+    """approx_quantiles for columns with a finite range that are not dense
+    integers, brackets located on the host: the CPU path, and on the GPU the
+    path of the columns that may need refinement. With `only`, a subset of
+    `cols` the device query flagged, just those columns are answered (and
+    returned); they keep their positions in `cols`, so the refinement passes
+    see the column indices of the whole call."""
+    probs_l = probs
+    picked = list(cols) if only is None else [c for c in cols if c in set(only)]
     lo = torch.tensor([moments[c].min for c in cols], dtype=torch.float64)
     hi = torch.tensor([moments[c].max for c in cols], dtype=torch.float64)
-    probs = list(probs)
 
     # pass-1 histograms are cached per column (range is always the global
     # min/max, so the CDF is reusable across quantile requests)
     key = ("hist", nbins)
-    todo = [i for i, c in enumerate(cols) if key not in idf.col(c).cache]
+    for c in picked:  # read by a device query already: fetch the row
+        cache = idf.col(c).cache
+        if key not in cache and ("hist_dev", nbins) in cache:
+            h, _, row = cache[("hist_dev", nbins)]
+            cache[key] = h[row].cpu()
+    pos = {c: i for i, c in enumerate(cols)}
+    todo = [pos[c] for c in picked if key not in idf.col(c).cache]
     if todo:
         tensors = [idf.col(cols[i]).data for i in todo]
         h = global_histograms(tensors, lo[todo], hi[todo], nbins).cpu()
@@ -288,42 +544,18 @@ def approx_quantiles(
             idf.col(cols[i]).cache[key] = h[k]
     import numpy as np
 
-    hist_np = torch.stack([idf.col(c).cache[key] for c in cols]).numpy().astype(np.float64)
-    cdf = np.cumsum(hist_np, axis=1)
+    # a column outside `picked` gets an empty row and n = 0: no brackets
+    skip = set(cols) - set(picked)
+    empty = torch.zeros(nbins, dtype=torch.int64)
+    hist_np = torch.stack([empty if c in skip else idf.col(c).cache[key] for c in cols]).numpy().astype(np.float64)
     tensors = [idf.col(c).data for c in cols]
 
     result = {c: [float("nan")] * len(probs) for c in cols}
-    # bracket per (col, prob): bin containing target rank — fully
-    # vectorized over the (col x prob) grid (the per-pair python loop
-    # cost ~5 ms/step at 150x9)
-    brackets = {}
-    top = set()  # brackets on the last pass-1 bin
-    probs_np = np.asarray(probs)
-    K, P = len(cols), len(probs)
-    ns = np.array([moments[c].n for c in cols], dtype=np.float64)
-    lows = lo.numpy().astype(np.float64)
+    ns = np.array([0.0 if c in skip else moments[c].n for c in cols], dtype=np.float64)
     highs = hi.numpy().astype(np.float64)
-    valid = (ns > 0) & (lows == lows)
-    degenerate = valid & (highs <= lows)
-    for i in np.nonzero(degenerate)[0]:
-        result[cols[i]] = [float(lows[i])] * P
-    active = np.nonzero(valid & ~degenerate)[0]
-    if active.size:
-        w = (highs[active] - lows[active]) / nbins  # [A]
-        targets = probs_np[None, :] * (ns[active, None] - 1)  # [A,P]
-        # vectorized per-row searchsorted: count of cdf entries < target
-        cdf_a = cdf[active]  # [A,nbins]
-        bs = np.minimum((cdf_a[:, :, None] < (targets + 0.5)[:, None, :]).sum(axis=1), nbins - 1)  # [A,P]
-        rows = np.arange(active.size)[:, None]
-        belows = np.where(bs > 0, cdf_a[rows, np.maximum(bs - 1, 0)], 0.0)
-        cnts = hist_np[active][rows, bs]
-        for a, i in enumerate(active):
-            l = lows[i]
-            wa = w[a]
-            for j in range(P):
-                b = int(bs[a, j])
-                brackets[(int(i), j)] = (l + b * wa, l + (b + 1) * wa, float(targets[a, j] - belows[a, j]), float(cnts[a, j]))
-        top = {(int(active[a]), int(j)) for a, j in zip(*np.nonzero(bs == nbins - 1))}
+    constant, active, brackets, top = _pass1_brackets(hist_np, lo.numpy(), highs, ns, probs)
+    for i, v in constant.items():
+        result[cols[i]] = [v] * len(probs)
     # adaptive: a bracket is refined while it holds > rel_err/2 of the rank
     # mass (any point of a bracket is within its count of the target rank,
     # so at that size the contract holds with half the tolerance to spare)
@@ -383,25 +615,14 @@ def approx_quantiles(
                 point[k] = mn
             else:
                 unresolved.add(k[0])
-    for (i, j), (bl, bh, off, cnt) in brackets.items():
-        c = cols[i]
-        if cnt <= 1 or bh <= bl:
-            result[c][j] = bl
-        else:
-            # interpolate inside the (now tiny) bracket by rank fraction
-            frac = min(max(off / max(cnt - 1, 1e-9), 0.0), 1.0) if cnt > 1 else 0.0
-            result[c][j] = bl + frac * (bh - bl)
-    for (i, j), v in point.items():
+    for (i, j), v in _bracket_values(brackets, point, top, highs).items():
         result[cols[i]][j] = v
-    for i, j in top:
-        # the last pass-1 bin's upper bound may round to just above the maximum
-        result[cols[i]][j] = min(result[cols[i]][j], float(highs[i]))
     if unresolved:
         result.update(_exact_quantiles(idf, [cols[i] for i in sorted(unresolved)], probs, moments, rel_err=rel_err))
-    for c in cols:
+    for c in picked:
         for j, p in enumerate(probs_l):
             idf.col(c).cache[("q", p)] = result[c][j]
-    return result
+    return {c: result[c] for c in picked}
 
 
 def _refine_pass(tensors, cols, brackets, nbins, col_lo=None, col_hi=None):
