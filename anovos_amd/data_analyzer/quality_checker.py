@@ -450,7 +450,11 @@ def outlier_detection(
             hi_t.append(float(hi) if use_hi else float("nan"))
         mode = 0 if not treatment else (1 if treatment_method == "value_replacement" else 2)
         tensors = [idf.col(c).data.contiguous() for c in list_of_cols]
-        counts, outs = ext.outlier_clamp_columns(tensors, torch.tensor(lo_t), torch.tensor(hi_t), mode)
+        # bounds travel as float64: the kernel gives the verdict of the
+        # double comparison, which a bound rounded to float32 would move
+        counts, outs = ext.outlier_clamp_columns(
+            tensors, torch.tensor(lo_t, dtype=torch.float64), torch.tensor(hi_t, dtype=torch.float64), mode
+        )
         counts = dist.all_reduce_(counts.to(torch.float64), "sum").cpu().to(torch.int64)
         for i, c in enumerate(list_of_cols):
             rows_print.append([c, int(counts[i, 0]), int(counts[i, 1]), 0])
@@ -471,10 +475,14 @@ def outlier_detection(
     for c, (lo, hi) in zip(list_of_cols, params):
         x = idf.col(c).data
         flag = torch.zeros_like(x, dtype=torch.int8)
+        # the verdict is that of the double comparison, as in the fused
+        # kernel: a float32 column against a Python scalar would compare
+        # in float32, with the bound rounded (NaN compares false)
+        xd = x.to(torch.float64)
         if detection_side in ("lower", "both") and lo is not None:
-            flag = torch.where((x < lo) & ~torch.isnan(x), torch.full_like(flag, -1), flag)
+            flag = torch.where(xd < float(lo), torch.full_like(flag, -1), flag)
         if detection_side in ("upper", "both") and hi is not None:
-            flag = torch.where((x > hi) & ~torch.isnan(x), torch.ones_like(flag), flag)
+            flag = torch.where(xd > float(hi), torch.ones_like(flag), flag)
         flags[c] = flag
         local_lo_hi.extend([int((flag == -1).sum()), int((flag == 1).sum())])
         if treatment and treatment_method in ("value_replacement", "null_replacement"):
@@ -483,8 +491,11 @@ def outlier_detection(
                 hi_v = float(hi) if hi is not None else float("nan")
             else:
                 lo_v = hi_v = float("nan")
-            y = torch.where(flags[c] == 1, torch.full_like(x, hi_v), x)
-            y = torch.where(flags[c] == -1, torch.full_like(x, lo_v), y)
+            # the bound rounded to the column's dtype, as the kernel writes it
+            # (full_like refuses a double beyond the float32 range)
+            lo_r, hi_r = (torch.tensor(v, dtype=torch.float64, device=x.device).to(x.dtype) for v in (lo_v, hi_v))
+            y = torch.where(flags[c] == 1, hi_r, x)
+            y = torch.where(flags[c] == -1, lo_r, y)
             odf = odf.with_column(c + "_outliered", Column(c + "_outliered", idf.col(c).dtype, y))
             if output_mode == "replace":
                 odf = odf.drop([c]).rename({c + "_outliered": c})

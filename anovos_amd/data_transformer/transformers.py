@@ -516,7 +516,9 @@ def IQR_standardization(
                 }
             )
             _save_model(dfm, model_path, "IQR_standardization")
-    excluded = [c for c in list_of_cols if round(params[c][2] - params[c][0], 5) == 0.0]
+    # a column without values has NaN quartiles: excluded like a constant one
+    iqr = {c: params[c][2] - params[c][0] for c in list_of_cols}
+    excluded = [c for c in list_of_cols if not (iqr[c] == iqr[c]) or round(iqr[c], 5) == 0.0]
     if excluded:
         warnings.warn("The following column(s) are excluded from standardization because IQR is zero:" + str(excluded))
     odf = idf

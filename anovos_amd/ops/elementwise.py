@@ -24,7 +24,14 @@ def fill_code_columns(tensors: Sequence[torch.Tensor], fills: Sequence[int]) -> 
 
 
 def scale_columns(tensors: Sequence[torch.Tensor], a: Sequence[float], b: Sequence[float]) -> List[torch.Tensor]:
-    """out_i = (x_i - a_i) * b_i as float32; NaN propagates."""
+    """out_i = float32((float64(x_i) - a_i) * b_i); NaN propagates.
+
+    The column is centred in double, with a_i and b_i as the doubles they
+    were fitted as, and the product is rounded to float32 once. The HIP
+    kernel (K11) and the torch path below compute this same formula for
+    float32 and float64 columns alike, so a column whose mean is large
+    against its spread keeps its signal, and min-max output stays inside
+    [0, 1]."""
     if tensors and tensors[0].is_cuda and backend.use_hip(tensors[0]):
         ext = backend.hip_ext()
         return ext.scale_columns(
@@ -32,7 +39,7 @@ def scale_columns(tensors: Sequence[torch.Tensor], a: Sequence[float], b: Sequen
             torch.tensor(list(a), dtype=torch.float64),
             torch.tensor(list(b), dtype=torch.float64),
         )
-    return [((t.to(torch.float32) - float(ai)) * float(bi)) for t, ai, bi in zip(tensors, a, b)]
+    return [((t.to(torch.float64) - float(ai)) * float(bi)).to(torch.float32) for t, ai, bi in zip(tensors, a, b)]
 
 
 def fill_nan_columns(tensors: Sequence[torch.Tensor], fills: Sequence[float]) -> List[torch.Tensor]:

@@ -1367,7 +1367,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lut_apply_f32", &lut_apply_f32, "fused LUT gather -> float (K12)");
   m.def("lut_apply_i32", &lut_apply_i32, "fused LUT gather -> int32 (K12)");
   m.def("hll_registers_multi", &hll_registers_multi, "fused multi-column HLL (K4)");
-  m.def("scale_columns", &scale_columns, "fused (x-a)*b scaling (K11)");
+  m.def("scale_columns", &scale_columns,
+        "fused scaling (K11): out = (float)(((double)x - a) * b), f32 and f64 columns alike");
   m.def("fill_nan_columns", &fill_nan_columns, "fused NaN fill (K11)");
   m.def("fill_code_columns", &fill_code_columns, "fused categorical null fill (K11)");
   m.def("column_moments", &column_moments, "fused per-column moments (K1/K2)",

@@ -1160,7 +1160,31 @@ __global__ __launch_bounds__(THREADS) void hll_multi_kernel(
 // ------------------------------------------------------------------
 // K11 fused: multi-column scale/shift  out = (x - a) * b   (NaN passes)
 //            and multi-column NaN fill out = isnan(x) ? fill : x
+//
+// The scale formula, for f32 and f64 columns alike, is
+//     out = (float)(((double)x - a) * b)
+// with a and b as the doubles they were fitted as: the column is centred
+// before anything is rounded to f32. Rounding x, a or the difference to
+// f32 first loses the signal of a column whose mean is large against
+// its spread (epoch seconds, cents, a year). The double chain also keeps
+// min-max output inside [0, 1]: (max - min) * (1 / (max - min)) is within
+// an ulp of 1 in double and rounds to 1.0f. A subtraction followed by a
+// multiplication: nothing to contract.
 // ------------------------------------------------------------------
+
+template <typename T>
+DEV_INLINE float axpb1(T x, double a, double b) {
+  return (float)(((double)x - a) * b);
+}
+
+DEV_INLINE nat_f4 axpb4(nat_f4 v, double a, double b) {
+  nat_f4 r;
+  r.x = axpb1(v.x, a, b);
+  r.y = axpb1(v.y, a, b);
+  r.z = axpb1(v.z, a, b);
+  r.w = axpb1(v.w, a, b);
+  return r;
+}
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void axpb_kernel(
@@ -1174,8 +1198,8 @@ __global__ __launch_bounds__(THREADS) void axpb_kernel(
   const int64_t per = chunk_rows(n, nchunks);
   const int64_t s = (int64_t)chunk * per;
   const int64_t e = min(n, s + per);
-  const float av = (float)a[col];
-  const float bv = (float)b[col];
+  const double av = a[col];
+  const double bv = b[col];
   if (sizeof(T) == 4) {
     // dwordx4 loads need only 4-byte alignment on CDNA — no head guard;
     // 2x unroll + non-temporal keeps two loads in flight per lane
@@ -1187,20 +1211,20 @@ __global__ __launch_bounds__(THREADS) void axpb_kernel(
     for (; i + THREADS < nv; i += 2 * THREADS) {
       nat_f4 v = __builtin_nontemporal_load(&xv[i]);
       nat_f4 w = __builtin_nontemporal_load(&xv[i + THREADS]);
-      v = (v - av) * bv;
-      w = (w - av) * bv;
+      v = axpb4(v, av, bv);
+      w = axpb4(w, av, bv);
       __builtin_nontemporal_store(v, &ov[i]);
       __builtin_nontemporal_store(w, &ov[i + THREADS]);
     }
     for (; i < nv; i += THREADS) {
       nat_f4 v = xv[i];
-      ov[i] = (v - av) * bv;
+      ov[i] = axpb4(v, av, bv);
     }
     for (int64_t j = s + nv * 4 + threadIdx.x; j < e; j += THREADS)
-      out[j] = ((float)x[j] - av) * bv;
+      out[j] = axpb1(x[j], av, bv);
   } else {
     for (int64_t i = s + threadIdx.x; i < e; i += THREADS)
-      out[i] = ((float)x[i] - av) * bv;
+      out[i] = axpb1(x[i], av, bv);
   }
 }
 

@@ -251,6 +251,9 @@ def spearman_matrix(idf, cols: List[str], cells: int = 1024, use_bf16: bool = Tr
     if dist.is_dist():
         dist.all_reduce_(gram, "sum")
     g = gram.cpu().numpy()
+    # X @ X.T goes through a general matrix product, which on some hosts
+    # leaves g[i, j] and g[j, i] an ulp apart; a symmetric g stays as it is
+    g = 0.5 * (g + g.T)
     d = np.sqrt(np.clip(np.diag(g), 1e-300, None))
     corr = g / np.outer(d, d)
     np.fill_diagonal(corr, 1.0)

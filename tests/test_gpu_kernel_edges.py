@@ -760,15 +760,16 @@ def _value_cols(seed):
 @requires_gpu
 @pytest.mark.gpu
 def test_scale_columns_bit_exact(ext):
-    """The kernel rounds a and b to f32, converts f64 input to f32 first
-    and computes (x - a) * b in f32: a subtraction followed by a
-    multiplication, nothing to contract."""
+    """The kernel widens x to f64, computes (x - a) * b in f64 with a and b
+    as given, and rounds the product to f32 once, for f32 and f64 columns
+    alike: a subtraction followed by a multiplication, nothing to
+    contract."""
     cols = _value_cols(97)
     a = torch.tensor([0.1 * (i + 1) for i in range(len(cols))], dtype=torch.float64)
     b = torch.tensor([(-1.0) ** i / (3.0 + i) for i in range(len(cols))], dtype=torch.float64)
     outs = ext.scale_columns([_dev(c, o) for c, o in cols], a, b)
     for i, (c, _) in enumerate(cols):
-        want = (c.float() - a[i].float()) * b[i].float()
+        want = ((c.double() - a[i]) * b[i]).float()
         assert outs[i].dtype == torch.float32
         _same_bits(outs[i], want, f"column {i}")
 

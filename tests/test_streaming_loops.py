@@ -133,6 +133,8 @@ def test_rho_guard_bit_equals_capped_rho(p):
 @requires_gpu
 @pytest.mark.gpu
 def test_scale_and_fill_nan(ext, value_sets):
+    """Scaling is (float)(((double)x - a) * b) with a and b as given;
+    the fill is rounded to the column's dtype."""
     for name, cols in value_sets:
         k = len(cols)
         dev = [_guarded(c, NAN if j % 3 else 7.0, j) for j, c in enumerate(cols)]
@@ -142,7 +144,7 @@ def test_scale_and_fill_nan(ext, value_sets):
         scaled = ext.scale_columns(dev, a, b)
         filled = ext.fill_nan_columns(dev, fill)
         for i, c in enumerate(cols):
-            _same_bits(scaled[i], (c - a[i].float()) * b[i].float(), f"{name} scale {i}")
+            _same_bits(scaled[i], ((c.double() - a[i]) * b[i]).float(), f"{name} scale {i}")
             _same_bits(filled[i], torch.where(torch.isnan(c), fill[i].float(), c), f"{name} fill {i}")
 
 
