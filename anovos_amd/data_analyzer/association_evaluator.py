@@ -3,6 +3,8 @@ data_analyzer/association_evaluator.py (586 LoC).
 
 - correlation_matrix (:38): bf16 MFMA Gram kernel / rocBLAS path (K8);
   method="spearman" (beyond the reference) ranks on a grid first (K24),
+  null_policy="pairwise" (beyond the reference) takes every entry over
+  the rows where both columns are present (masked Gram kernel, K25),
 - variable_clustering (:142): one fused covariance pass + driver-side
   VarClusHi (association_eval_varclus.py),
 - IV_calculation (:253): per-bin label histograms (K9) + WOE/IV sums,
@@ -39,7 +41,7 @@ from anovos_amd.shared.tracing import traced
 
 
 @traced
-def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=False, sample_size=1000000, print_impact=False, use_bf16=True, method="pearson", rank_cells=1024):
+def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=False, sample_size=1000000, print_impact=False, use_bf16=True, method="pearson", rank_cells=1024, null_policy="mean", min_periods=2):
     """[attribute, <cols...>] — reference association_evaluator.py:38-139.
 
     use_bf16=True (default) runs the hand-written bf16 MFMA Gram kernel:
@@ -55,9 +57,32 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
     through the same Gram paths. Ranks are taken among a column's non-null
     rows and a null takes the mean rank, so it contributes zero — the
     Pearson path's convention. Rows that share a cell are tied; a column
-    with at most `rank_cells` distinct values or rows is ranked exactly."""
+    with at most `rank_cells` distinct values or rows is ranked exactly.
+
+    null_policy="mean" (default) is the behaviour above: a null counts as
+    the column mean and contributes zero to every sum — right on the
+    imputed frame the workflow hands over. null_policy="pairwise" (the
+    reference has neither keyword) is for a raw frame: every entry is
+    Pearson's r over the rows where BOTH columns are present, as pandas
+    `DataFrame.corr` and R `use="pairwise.complete.obs"` compute it, from
+    one pass of the masked MFMA Gram kernel (K25; `use_bf16=False` takes
+    f32 rocBLAS matmuls, the CPU backend fp64). An entry, diagonal
+    included, is NaN where fewer than max(min_periods, 2) rows have both
+    values or where either column is constant on those rows (see
+    ops/corr.py for the thresholds); `pairwise_observation_counts` returns
+    the row count behind each entry. Pearson only: Spearman ranks would
+    have to be retaken per pair."""
     if method not in ("pearson", "spearman"):
         raise TypeError("Invalid input for method: 'pearson' or 'spearman'")
+    if null_policy not in ("mean", "pairwise"):
+        raise TypeError("Invalid input for null_policy: 'mean' or 'pairwise'")
+    if isinstance(min_periods, bool) or not isinstance(min_periods, (int, np.integer)) or min_periods < 1:
+        raise TypeError("Invalid input for min_periods: an integer >= 1")
+    if null_policy == "pairwise" and method == "spearman":
+        raise TypeError(
+            "Invalid input for null_policy: 'pairwise' is not available with method='spearman' "
+            "(ranks would have to be retaken per pair of columns)"
+        )
     if (
         isinstance(rank_cells, bool) or not isinstance(rank_cells, (int, np.integer))
         or not 2 <= rank_cells <= rank_ops.GRADE_MAX_CELLS
@@ -76,6 +101,8 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
         idf = data_sample(idf, fraction=float(sample_size) / idf.count(), method_type="random")
     if method == "spearman":
         corr = rank_ops.spearman_matrix(idf, cols, cells=int(rank_cells), use_bf16=use_bf16)
+    elif null_policy == "pairwise":
+        corr = corr_ops.pairwise_pearson_matrix(idf, cols, use_bf16=use_bf16, min_periods=int(min_periods))
     else:
         corr = corr_ops.pearson_matrix(idf, cols, use_bf16=use_bf16)
     odf = pd.DataFrame(corr, columns=cols, index=cols)
@@ -84,6 +111,25 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
     odf = odf[["attribute"] + sorted_cols].sort_values("attribute").reset_index(drop=True)
     if print_impact:
         print(odf.to_string(index=False))
+    return odf
+
+
+@traced
+def pairwise_observation_counts(ctx, idf, list_of_cols="all", drop_cols=[]):
+    """[attribute, <cols...>] of int64 counts: the rows where both columns
+    are present — the denominator behind each entry of
+    correlation_matrix(null_policy="pairwise"); the diagonal is a column's
+    non-null count. Same shape and ordering as correlation_matrix."""
+    num_cols = attributeType_segregation(idf)[0]
+    if list_of_cols == "all":
+        list_of_cols = num_cols
+    cols = normalize_columns(idf, list_of_cols, drop_cols, restrict_to=num_cols)
+    if any(x not in num_cols for x in cols) or len(cols) == 0:
+        raise TypeError("Invalid input for Column(s)")
+    counts = np.rint(corr_ops.pairwise_sums(idf, cols)[0]).astype(np.int64)
+    odf = pd.DataFrame(counts, columns=cols, index=cols)
+    odf["attribute"] = odf.index
+    odf = odf[["attribute"] + sorted(cols)].sort_values("attribute").reset_index(drop=True)
     return odf
 
 

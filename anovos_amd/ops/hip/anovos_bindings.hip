@@ -1,5 +1,6 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
-// corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip). Compiled by torch.utils.cpp_extension
+// corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
+// pairwise_gram.hip). Compiled by torch.utils.cpp_extension
 // with hipcc for gfx950; streams come from the caller's current torch HIP
 // stream so kernels compose with the engine's side-stream overlap
 // (core/dist.py SideStream).
@@ -700,6 +701,57 @@ torch::Tensor centered_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
   return gram;
 }
 
+// K25: pairwise-complete Gram sums, fp64 [4, k, k] = (N, P, S, Q) with
+// m = !isnan(x), z = m ? x - mean : 0: N = sum m_i m_j, P = sum z_i z_j,
+// S[i][j] = sum z_i m_j, Q[i][j] = sum z_i^2 m_j (pairwise_gram.hip).
+torch::Tensor pairwise_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor means) {
+  ColumnBatch b = gather_columns(cols, "pairwise_gram_bf16", F32, /*equal_len=*/true);
+  check_count((size_t)means.numel(), cols.size(), b.name, "means");
+  TORCH_CHECK(means.device() == b.device, b.name, ": means must be on the columns' device");
+  auto device = b.device;
+  const int k = b.ncols();
+  const int64_t n = b.maxn;
+  auto means_d = means.to(torch::kFloat32).contiguous();
+  const int groups = (k + 16 * PAIRGRAM_GROUP_TILES - 1) / (16 * PAIRGRAM_GROUP_TILES);
+  std::vector<int> gi_h, gj_h;
+  for (int i = 0; i < groups; ++i)
+    for (int j = i; j < groups; ++j) {
+      gi_h.push_back(i);
+      gj_h.push_back(j);
+    }
+  const int64_t nitems = (int64_t)gi_h.size();
+  // Row split: one wave of resident blocks over all items (see
+  // anovos_gram_sr_grid), at least the split that keeps every block below
+  // PAIRGRAM_MAX_BLOCK_ROWS rows (its fp32 counts are exact up to there; a
+  // forced smaller split is raised to it), at most one macro-slab per block.
+  const int64_t macro_total = (n + PAIRGRAM_SLAB_ROWS - 1) / PAIRGRAM_SLAB_ROWS;
+  const int64_t macro_cap = PAIRGRAM_MAX_BLOCK_ROWS / PAIRGRAM_SLAB_ROWS - 1;
+  const int64_t min_chunks = std::max<int64_t>(1, (macro_total + macro_cap - 1) / macro_cap);
+  const int64_t capacity = std::max(1, anovos_pairwise_gram_grid());
+  int64_t target_chunks = std::max<int64_t>(1, capacity / nitems);
+  if (const char *e = getenv("ANOVOS_PAIRGRAM_CHUNKS")) target_chunks = atoll(e);
+  const int row_chunks = (int)std::max<int64_t>(
+      min_chunks, std::min<int64_t>(target_chunks, std::max<int64_t>(1, macro_total)));
+  // Items per launch: what one wave of blocks holds, so that the partials
+  // stay bounded however many groups k makes.
+  const int64_t per_launch = std::max<int64_t>(1, std::min(nitems, capacity / row_chunks));
+  auto gi = upload(gi_h, device);
+  auto gj = upload(gj_h, device);
+  auto dptr = upload(b.ptrs, device);
+  auto out = torch::zeros({4, k, k}, on(device, torch::kFloat64));
+  auto partials = torch::empty({(int64_t)row_chunks * per_launch, PAIRGRAM_ITEM_FLOATS},
+                               on(device, torch::kFloat32));
+  for (int64_t item0 = 0; item0 < nitems; item0 += per_launch) {
+    const int cnt = (int)std::min(per_launch, nitems - item0);
+    check_hip(anovos_pairwise_gram(ptr_table<const void>(dptr), n, k, means_d.data_ptr<float>(),
+                                   gi.data_ptr<int>() + item0, gj.data_ptr<int>() + item0, cnt,
+                                   row_chunks, partials.data_ptr<float>(),
+                                   out.data_ptr<double>(), current_stream()),
+              "anovos_pairwise_gram");
+  }
+  return out;
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1360,6 +1412,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cols"), py::arg("p"), py::arg("shifts") = std::vector<double>(),
         py::arg("null_masks") = false);
   m.def("centered_gram_bf16", &centered_gram_bf16, "bf16 MFMA centered Gram X^T X (K8)");
+  m.def("pairwise_gram_bf16", &pairwise_gram_bf16,
+        "bf16 MFMA pairwise-complete sums [4, k, k] = (N, P, S, Q) (K25)");
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

@@ -2,7 +2,7 @@
 //
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
-// grouped_moments.hip, grades.hip):
+// grouped_moments.hip, grades.hip, pairwise_gram.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -50,6 +50,14 @@ constexpr int GRADE_MAX_CELLS = 4096;
 // K3q: bins (or dense integer counts) of one column whose CDF the
 // quantile-query kernels hold in LDS as uint64
 constexpr int QQ_MAX_BINS = 4096;
+// K25: 16-column tiles per column group (a work item is a pair of groups),
+// rows of the macro-slab a block stages per round, fp32 partials one block
+// writes (tile pairs x 6 products x 256), and the rows one block may own:
+// its fp32 count accumulators are exact below 2^24
+constexpr int PAIRGRAM_GROUP_TILES = 4;
+constexpr int PAIRGRAM_SLAB_ROWS = 64;
+constexpr int PAIRGRAM_ITEM_FLOATS = PAIRGRAM_GROUP_TILES * PAIRGRAM_GROUP_TILES * 6 * 256;
+constexpr int64_t PAIRGRAM_MAX_BLOCK_ROWS = (int64_t)1 << 24;
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -187,4 +195,11 @@ int anovos_grade_apply(const void *const *cols, const int64_t *lens, int ncols,
                        const int *cutoff_len, const float *tabflat, const int64_t *tab_off,
                        float null_grade, int max_ncut, int nchunks, int dtype,
                        float *const *outs, hipStream_t stream);
+// pairwise_gram.hip: out is fp64 [4, k, k] = (N, P, S, Q); items are pairs
+// of column groups (item_gi[t] <= item_gj[t]); partials holds
+// row_chunks * nitems * PAIRGRAM_ITEM_FLOATS floats
+int anovos_pairwise_gram(const void *const *cols, int64_t n, int k, const float *means,
+                         const int *item_gi, const int *item_gj, int nitems, int row_chunks,
+                         float *partials, double *out, hipStream_t stream);
+int anovos_pairwise_gram_grid();
 }
