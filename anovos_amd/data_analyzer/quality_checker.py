@@ -518,6 +518,157 @@ def outlier_detection(
 
 
 @traced
+def multivariate_outlier_detection(
+    ctx,
+    idf,
+    list_of_cols="all",
+    drop_cols=[],
+    confidence=0.999,
+    threshold=None,
+    rank_tol=1e-6,
+    treatment=False,
+    append_distance=False,
+    distance_col="mahalanobis_d2",
+    pre_existing_model=False,
+    model_path="NA",
+    sample_size=1000000,
+    print_impact=False,
+):
+    """Beyond the reference (whose outlier_detection is univariate): rows
+    whose combination of values is improbable although every coordinate
+    may be ordinary. The squared Mahalanobis distance of every row,
+    d2 = (x - mu)^T Sigma^+ (x - mu) over the numerical columns
+    (ops/mahalanobis.py; on the GPU the MFMA kernel K26), is compared in
+    double against `threshold`, by default the chi-square quantile
+    chi2.ppf(confidence, rank). The model (mu, sd, whitening matrix) is
+    fitted on a sample of `sample_size` rows when the frame is larger; the
+    distance is always taken on the full frame. A null counts as the
+    column mean. treatment=True removes the flagged rows;
+    append_distance=True appends d2 as the f32 column `distance_col`."""
+    from anovos_amd.ops import mahalanobis as maha_ops
+
+    num_cols = attributeType_segregation(idf)[0]
+    treatment = _parse_bool(treatment)
+    append_distance = _parse_bool(append_distance, "append_distance")
+    pre_existing_model = _parse_bool(pre_existing_model, "pre_existing_model")
+    if list_of_cols == "all":
+        list_of_cols = num_cols
+    list_of_cols = normalize_columns(idf, list_of_cols, drop_cols, restrict_to=num_cols)
+    if any(x not in num_cols for x in list_of_cols):
+        raise TypeError("Invalid input for Column(s)")
+    if isinstance(confidence, bool) or not isinstance(confidence, (int, float)) or not 0 < confidence < 1:
+        raise TypeError("Invalid input for confidence: a value between 0 and 1 (exclusive)")
+    if threshold is not None and (
+        isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not threshold > 0
+    ):
+        raise TypeError("Invalid input for threshold: a positive number")
+    if isinstance(rank_tol, bool) or not isinstance(rank_tol, (int, float)) or not 0 <= rank_tol < 1:
+        raise TypeError("Invalid input for rank_tol: a value in [0, 1)")
+    if append_distance and distance_col in idf.columns:
+        raise TypeError(f"Invalid input for distance_col: column '{distance_col}' already exists")
+
+    if pre_existing_model:
+        dfm = _load_model(model_path, "outlier_multivariate")
+        missing = [c for c in dfm["attribute"] if c not in idf.columns]
+        if missing:
+            raise TypeError(f"Invalid input for Column(s): model attributes not in the frame: {missing}")
+        used = dfm[dfm["sd"] > 0]
+        excluded = [str(c) for c in dfm[~(dfm["sd"] > 0)]["attribute"]]
+        W = np.array([list(w) for w in used["W"]], dtype=np.float64).T  # [r, k]
+        model = maha_ops.WhiteningModel(
+            [str(c) for c in used["attribute"]],
+            used["mean"].to_numpy(dtype=np.float64),
+            used["sd"].to_numpy(dtype=np.float64),
+            np.ascontiguousarray(W),
+            int(dfm["rank"].iloc[0]),
+            excluded,
+        )
+        if any(c not in num_cols for c in model.columns):
+            raise TypeError("Invalid input for Column(s)")
+        model_threshold = float(dfm["threshold"].iloc[0])
+    else:
+        if len(list_of_cols) < 2:
+            raise TypeError("Invalid input for Column(s): at least 2 numerical columns are needed")
+        if len(list_of_cols) > maha_ops.ROWQUAD_MAX_COLS:
+            raise TypeError(
+                f"Invalid input for Column(s): at most {maha_ops.ROWQUAD_MAX_COLS} numerical columns (ROWQUAD_MAX_COLS)"
+            )
+        idf_count = idf.count()
+        if idf_count > sample_size:
+            from anovos_amd.data_ingest.data_sampling import data_sample
+
+            idf_sample = data_sample(idf.select(list_of_cols), fraction=sample_size / idf_count, method_type="random", seed_value=11)
+        else:
+            idf_sample = idf.select(list_of_cols)
+        model = maha_ops.fit_whitening(idf_sample, list_of_cols, rank_tol=rank_tol)
+        model_threshold = None
+    if len(model.columns) < 2 or model.rank < 1:
+        raise TypeError("Invalid input for Column(s): fewer than 2 numerical columns with a non-zero variance")
+    if len(model.columns) > maha_ops.ROWQUAD_MAX_COLS:
+        raise TypeError(f"Invalid input for Column(s): at most {maha_ops.ROWQUAD_MAX_COLS} numerical columns (ROWQUAD_MAX_COLS)")
+    if model.excluded:
+        warnings.warn("Columns excluded from multivariate outlier detection (constant): " + ",".join(model.excluded))
+
+    if threshold is not None:
+        cut = float(threshold)
+    elif model_threshold is not None:
+        cut = model_threshold
+    else:
+        from scipy.stats import chi2
+
+        cut = float(chi2.ppf(confidence, model.rank))
+    if model_path != "NA" and not pre_existing_model:
+        k_all = len(model.columns) + len(model.excluded)
+        dfm = pd.DataFrame(
+            {
+                "attribute": model.columns + model.excluded,
+                "mean": list(model.mean) + [float("nan")] * len(model.excluded),
+                "sd": list(model.sd) + [0.0] * len(model.excluded),
+                # column j of W, the r weights of attribute j
+                "W": [model.W[:, j].tolist() for j in range(len(model.columns))] + [[] for _ in model.excluded],
+                "rank": [model.rank] * k_all,
+                "threshold": [cut] * k_all,
+            }
+        )
+        _save_model(dfm, model_path, "outlier_multivariate")
+
+    d2 = maha_ops.mahalanobis_d2(idf, model.columns, model)
+    # the verdict is that of the double comparison, as K10's
+    flag = d2.to(torch.float64) > cut
+    # one batched collective on every rank, empty shards included: the
+    # count is summed, the maximum travels in a slot per rank
+    world, me = dist.world_size(), dist.rank()
+    local = [float(flag.sum())] + [0.0] * world
+    local[1 + me] = float(d2.max()) if d2.numel() else 0.0
+    merged = dist.all_reduce_scalars(local)
+    outlier_rows = int(round(merged[0]))
+    max_distance = max(merged[1:])
+    rows_count = idf.count()
+
+    odf = idf
+    if append_distance:
+        odf = odf.with_column(distance_col, Column(distance_col, "float", d2))
+    if treatment:
+        odf = odf.filter_rows(~flag)
+    odf_print = pd.DataFrame(
+        [
+            ["rows_count", float(rows_count)],
+            ["attributes_count", float(len(model.columns))],
+            ["rank", float(model.rank)],
+            ["threshold", cut],
+            ["outlier_rows", float(outlier_rows)],
+            ["outlier_pct", round(outlier_rows / rows_count, 4) if rows_count else 0.0],
+            ["max_distance", float(max_distance)],
+            ["excluded_constant_attributes", ",".join(model.excluded)],
+        ],
+        columns=["metric", "value"],
+    )
+    if print_impact:
+        print(odf_print.to_string(index=False))
+    return odf, odf_print
+
+
+@traced
 def IDness_detection(ctx, idf, list_of_cols="all", drop_cols=[], treatment=False, treatment_threshold=0.8, stats_unique={}, print_impact=False):
     """Reference quality_checker.py:1048-1183."""
     if list_of_cols == "all":

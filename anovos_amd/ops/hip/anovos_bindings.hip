@@ -1,6 +1,6 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
-// pairwise_gram.hip). Compiled by torch.utils.cpp_extension
+// pairwise_gram.hip, row_quadform.hip). Compiled by torch.utils.cpp_extension
 // with hipcc for gfx950; streams come from the caller's current torch HIP
 // stream so kernels compose with the engine's side-stream overlap
 // (core/dist.py SideStream).
@@ -752,6 +752,51 @@ torch::Tensor pairwise_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
   return out;
 }
 
+// K26: d2[n] = |W z|^2 per row, z_j = isnan(x_j) ? 0 : (x_j - shift_j) * scale_j,
+// split-bf16 MFMA with fp32 accumulation (row_quadform.hip). W is [r, k],
+// r <= k; where its two bf16 planes do not fit in LDS beside the slab, one
+// launch per window of its rows, the later ones adding into d2.
+torch::Tensor row_quadform_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor shift,
+                                  torch::Tensor scale, torch::Tensor W) {
+  ColumnBatch b = gather_columns(cols, "row_quadform_bf16x2", F32, /*equal_len=*/true);
+  check_count((size_t)shift.numel(), cols.size(), b.name, "shift");
+  check_count((size_t)scale.numel(), cols.size(), b.name, "scale");
+  TORCH_CHECK(W.dim() == 2 && W.is_floating_point(), b.name,
+              ": W must be a 2-D floating-point tensor");
+  const int64_t k = b.ncols();
+  const int64_t r = W.size(0);
+  TORCH_CHECK(W.size(1) == k, b.name, ": W has ", W.size(1), " columns, expected ", k);
+  TORCH_CHECK(k <= ROWQUAD_MAX_COLS, b.name, ": ", k, " columns, at most ", ROWQUAD_MAX_COLS,
+              " (ROWQUAD_MAX_COLS)");
+  TORCH_CHECK(r >= 1 && r <= k, b.name, ": W has ", r, " rows, expected 1 .. ", k);
+  TORCH_CHECK(shift.device() == b.device && scale.device() == b.device && W.device() == b.device,
+              b.name, ": shift, scale and W must be on the columns' device");
+  auto device = b.device;
+  const int64_t n = b.maxn;
+  auto out = torch::empty({n}, on(device, torch::kFloat32));
+  if (n == 0) return out;
+  auto shift_d = shift.to(torch::kFloat32).contiguous();
+  auto scale_d = scale.to(torch::kFloat32).contiguous();
+  auto W_d = W.to(torch::kFloat32).contiguous();
+  const int r_pad = rowquad_rpad((int)r), k_pad = rowquad_kpad((int)k);
+  auto wimg = torch::empty({2 * (int64_t)(k_pad / 8) * r_pad * 8}, on(device, torch::kInt16));
+  auto dptr = upload(b.ptrs, device);
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_ROWQUAD_BLOCKS")) blocks = atoi(e);
+  check_hip(anovos_row_quadform_split(W_d.data_ptr<float>(), (int)r, (int)k,
+                                      (uint16_t *)wimg.data_ptr<int16_t>(), current_stream()),
+            "anovos_row_quadform_split");
+  const int window = rowquad_window_rows((int)k);
+  for (int r0 = 0; r0 < r_pad; r0 += window)
+    check_hip(anovos_row_quadform(ptr_table<const void>(dptr), n, (int)k,
+                                  shift_d.data_ptr<float>(), scale_d.data_ptr<float>(),
+                                  (const uint16_t *)wimg.data_ptr<int16_t>(), (int)r, r0,
+                                  std::min(window, r_pad - r0), /*accumulate=*/r0 > 0, blocks,
+                                  out.data_ptr<float>(), current_stream()),
+              "anovos_row_quadform");
+  return out;
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1414,6 +1459,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("centered_gram_bf16", &centered_gram_bf16, "bf16 MFMA centered Gram X^T X (K8)");
   m.def("pairwise_gram_bf16", &pairwise_gram_bf16,
         "bf16 MFMA pairwise-complete sums [4, k, k] = (N, P, S, Q) (K25)");
+  m.def("row_quadform_bf16x2", &row_quadform_bf16x2,
+        "per-row |W z|^2 of standardized columns, split-bf16 MFMA (K26)");
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

@@ -2,7 +2,7 @@
 //
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
-// grouped_moments.hip, grades.hip, pairwise_gram.hip):
+// grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -58,6 +58,30 @@ constexpr int PAIRGRAM_GROUP_TILES = 4;
 constexpr int PAIRGRAM_SLAB_ROWS = 64;
 constexpr int PAIRGRAM_ITEM_FLOATS = PAIRGRAM_GROUP_TILES * PAIRGRAM_GROUP_TILES * 6 * 256;
 constexpr int64_t PAIRGRAM_MAX_BLOCK_ROWS = (int64_t)1 << 24;
+// K26: most columns of a row quadratic form, rows of the slab a block
+// stages per round, and the LDS of one block (all of a CU's): the Z slab
+// (two bf16 planes, one 16-byte slot per column octet and row,
+// ROWQUAD_Z_SLOTS slots per octet) beside the window of W's rows that stays
+// resident (two bf16 planes of k_pad columns). Columns pad to 32 (an MFMA
+// k-step), W's rows to 16 (a tile). The window plan depends only on k: at
+// k_pad = 160 all 160 rows fit (43 520 + 102 400 B), at k_pad = 256 80 do.
+constexpr int ROWQUAD_MAX_COLS = 256;
+constexpr int ROWQUAD_SLAB_ROWS = 64;
+constexpr int ROWQUAD_Z_SLOTS = 68;
+constexpr int ROWQUAD_LDS_BYTES = 160 * 1024;
+__host__ __device__ constexpr int rowquad_kpad(int k) { return (k + 31) / 32 * 32; }
+__host__ __device__ constexpr int rowquad_rpad(int r) { return (r + 15) / 16 * 16; }
+__host__ __device__ constexpr int rowquad_z_bytes(int k_pad) {
+  return 2 * (k_pad / 8) * ROWQUAD_Z_SLOTS * 16;
+}
+__host__ __device__ constexpr int rowquad_w_row_bytes(int k_pad) { return 2 * (k_pad / 8) * 16; }
+// rows of W (a multiple of 16) one launch keeps in LDS
+__host__ __device__ constexpr int rowquad_window_rows(int k) {
+  return (ROWQUAD_LDS_BYTES - rowquad_z_bytes(rowquad_kpad(k))) /
+         rowquad_w_row_bytes(rowquad_kpad(k)) / 16 * 16;
+}
+static_assert(rowquad_window_rows(160) >= 160, "the 150-column benchmark frame takes one launch");
+static_assert(rowquad_window_rows(ROWQUAD_MAX_COLS) >= 16, "a window holds at least one tile");
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -202,4 +226,14 @@ int anovos_pairwise_gram(const void *const *cols, int64_t n, int k, const float 
                          const int *item_gi, const int *item_gj, int nitems, int row_chunks,
                          float *partials, double *out, hipStream_t stream);
 int anovos_pairwise_gram_grid();
+// row_quadform.hip: wimg holds the two bf16 planes of W [r, k] as
+// 2 * (k_pad / 8) * r_pad * 8 uint16 (anovos_row_quadform_split fills it,
+// once per call); one launch takes the rows [r0, r0 + rw_pad) of it, both
+// multiples of 16 with rw_pad <= rowquad_window_rows(k), and writes
+// (accumulate = 0) or adds to (1) out[n]. blocks <= 0: one wave of resident
+// blocks.
+int anovos_row_quadform_split(const float *W, int r, int k, uint16_t *wimg, hipStream_t stream);
+int anovos_row_quadform(const void *const *cols, int64_t n, int k, const float *shift,
+                        const float *scale, const uint16_t *wimg, int r, int r0, int rw_pad,
+                        int accumulate, int blocks, float *out, hipStream_t stream);
 }

@@ -30,6 +30,7 @@ def build(verbose: bool = True) -> str:
             os.path.join(HERE, "grouped_moments.hip"),
             os.path.join(HERE, "grades.hip"),
             os.path.join(HERE, "pairwise_gram.hip"),
+            os.path.join(HERE, "row_quadform.hip"),
         ],
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],
