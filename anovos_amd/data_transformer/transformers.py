@@ -426,6 +426,32 @@ def cat_to_num_supervised(
 
 
 # ---------------- scaling ----------------
+def _z_standardization_params(idf, list_of_cols, pre_existing_model=False, model_path="NA"):
+    """The model of z_standardization, shared with PCA_latentFeatures, which
+    can apply it inside its projection: {column: (mean, stddev)} fitted from
+    frame_moments (and saved under model_path) or loaded from model_path,
+    the columns excluded for a zero standard deviation (with the warning),
+    and the fitted moments (None for a loaded model)."""
+    moments = None
+    if pre_existing_model:
+        dfm = _load_model(model_path, "z_standardization")
+        params = dict(zip(dfm["feature"], zip(dfm["mean"], dfm["stddev"])))
+    else:
+        moments = stats_ops.frame_moments(idf, list_of_cols)
+        params = {c: (moments[c].mean, moments[c].stddev) for c in list_of_cols}
+        if model_path != "NA":
+            dfm = pd.DataFrame(
+                {"feature": list_of_cols, "mean": [params[c][0] for c in list_of_cols], "stddev": [params[c][1] for c in list_of_cols]}
+            )
+            _save_model(dfm, model_path, "z_standardization")
+    excluded = [c for c in list_of_cols if c not in params or not (params[c][1] == params[c][1]) or round(params[c][1], 5) == 0.0]
+    if excluded:
+        warnings.warn(
+            "The following column(s) are excluded from standardization because the standard deviation is zero:" + str(excluded)
+        )
+    return params, excluded, moments
+
+
 @traced
 def z_standardization(
     ctx,
@@ -447,22 +473,7 @@ def z_standardization(
         warnings.warn("No Standardization Performed - No numerical column(s) to transform")
         return idf
 
-    if pre_existing_model:
-        dfm = _load_model(model_path, "z_standardization")
-        params = dict(zip(dfm["feature"], zip(dfm["mean"], dfm["stddev"])))
-    else:
-        moments = stats_ops.frame_moments(idf, list_of_cols)
-        params = {c: (moments[c].mean, moments[c].stddev) for c in list_of_cols}
-        if model_path != "NA":
-            dfm = pd.DataFrame(
-                {"feature": list_of_cols, "mean": [params[c][0] for c in list_of_cols], "stddev": [params[c][1] for c in list_of_cols]}
-            )
-            _save_model(dfm, model_path, "z_standardization")
-    excluded = [c for c in list_of_cols if c not in params or not (params[c][1] == params[c][1]) or round(params[c][1], 5) == 0.0]
-    if excluded:
-        warnings.warn(
-            "The following column(s) are excluded from standardization because the standard deviation is zero:" + str(excluded)
-        )
+    params, excluded, _ = _z_standardization_params(idf, list_of_cols, pre_existing_model, model_path)
     odf = idf
     applied = [c for c in list_of_cols if c not in excluded]
     if applied:

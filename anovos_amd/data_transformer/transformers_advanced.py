@@ -389,10 +389,18 @@ def PCA_latentFeatures(
     print_impact=False,
 ):
     """PCA with k chosen by explained-variance cutoff — reference
-    transformers.py:2915-3168. Covariance via the K8 Gram path, driver
-    eigh, on-device projection GEMM."""
+    transformers.py:2915-3168. Covariance in fp64, driver eigh, scores from
+    the K27 projection kernel (ops/project.py): every latent column is a
+    contiguous tensor of its own. With output_mode="replace" the
+    standardization is applied inside the projection (shift = mean, scale =
+    1 / stddev) and the standardized frame is not materialised - provided
+    standardization_configs holds no key besides pre_existing_model and
+    model_path and the frame has at most 256 columns; otherwise, as with
+    output_mode="append" or imputation=True, z_standardization runs first
+    and its output (one more frame-sized allocation) is projected."""
     from anovos_amd.data_transformer import transformers as T
     from anovos_amd.ops import corr as corr_ops
+    from anovos_amd.ops import project as project_ops
 
     num_cols = attributeType_segregation(idf)[0]
     if list_of_cols == "all":
@@ -404,38 +412,79 @@ def PCA_latentFeatures(
     work = idf
     if imputation:
         work = T.imputation_MMM(ctx, work, cols)
-    if standardization:
+    shift = np.zeros(len(cols))
+    scale = np.ones(len(cols))
+    moments = None
+    # the standardization folds into the projection where its output is not
+    # part of the result and the model is z_standardization's plain one
+    fused = (
+        standardization
+        and output_mode == "replace"
+        and len(cols) <= project_ops.PROJECT_MAX_COLS
+        and set(standardization_configs) <= {"pre_existing_model", "model_path"}
+    )
+    if fused:
+        params, excluded, moments = T._z_standardization_params(work, cols, **standardization_configs)
+        for i, c in enumerate(cols):
+            if c not in excluded:
+                shift[i], scale[i] = params[c][0], 1.0 / params[c][1]
+    elif standardization:
         work = T.z_standardization(ctx, work, cols, **standardization_configs)
 
     if pre_existing_model:
         comp = pd.read_parquet(os.path.join(model_path, "PCA_latentFeatures", "components.parquet"))
-        W = torch.tensor(comp.values, dtype=torch.float32, device=idf.device)
+        W = np.ascontiguousarray(comp.values, dtype=np.float32)  # [columns, k]
         k = W.shape[1]
     else:
-        cov = corr_ops.covariance_matrix(work, cols)
+        cov = corr_ops.covariance_matrix(work, cols, moments=moments)
+        if fused:  # of the standardized columns: D cov D, D = diag(scale)
+            cov = cov * np.outer(scale, scale)
         vals, vecs = np.linalg.eigh(cov)
         order = np.argsort(vals)[::-1]
         vals, vecs = vals[order], vecs[:, order]
         ratio = np.cumsum(vals) / max(np.sum(vals), 1e-300)
         k = int(np.searchsorted(ratio, explained_variance_cutoff) + 1)
         k = max(1, min(k, len(cols)))
-        W = torch.tensor(np.ascontiguousarray(vecs[:, :k]), dtype=torch.float32, device=idf.device)
+        W = np.ascontiguousarray(vecs[:, :k], dtype=np.float32)
         if model_path != "NA" and dist.rank() == 0:
             d = os.path.join(model_path, "PCA_latentFeatures")
             os.makedirs(d, exist_ok=True)
-            pd.DataFrame(W.cpu().numpy(), index=cols).to_parquet(os.path.join(d, "components.parquet"))
+            pd.DataFrame(W, index=cols).to_parquet(os.path.join(d, "components.parquet"))
         dist.barrier()
-    X = torch.stack([torch.nan_to_num(work.col(c).data.to(torch.float32), nan=0.0) for c in cols], dim=1)
-    Z = X @ W  # rocBLAS GEMM on device
+    if len(cols) <= project_ops.PROJECT_MAX_COLS:
+        latents = project_ops.project_columns(work, cols, shift, scale, W.T)
+    else:
+        latents = _project_library(work, cols, torch.tensor(W, device=idf.device))
     odf = work
     for j in range(k):
         name = f"latent_{j}"
-        odf = odf.with_column(name, Column(name, "double", Z[:, j]))
+        odf = odf.with_column(name, Column(name, "double", latents[j]))
     if output_mode == "replace":
         odf = odf.drop(cols)
     if print_impact:
         print(f"PCA: {k} latent features (cutoff {explained_variance_cutoff})")
     return odf
+
+
+# Scratch of one row slab of _project_library (the f32 X block and its scores).
+_PCA_SLAB_BYTES = 1 << 28
+
+
+def _project_library(work, cols, W):
+    """Scores of a frame wider than the projection kernel takes: per row
+    slab X = nan_to_num(columns) as f32 [rows, columns], X @ W through
+    rocBLAS, every component copied into a tensor of its own."""
+    tensors = [work.col(c).data for c in cols]
+    n, k = int(tensors[0].shape[0]), W.shape[1]
+    outs = [torch.empty(n, dtype=torch.float32, device=W.device) for _ in range(k)]
+    rows = max(1, _PCA_SLAB_BYTES // (4 * (len(cols) + k)))
+    for r0 in range(0, n, rows):
+        r1 = min(n, r0 + rows)
+        X = torch.stack([torch.nan_to_num(t[r0:r1].to(torch.float32), nan=0.0) for t in tensors], dim=1)
+        Z = X @ W
+        for j in range(k):
+            outs[j][r0:r1] = Z[:, j]
+    return outs
 
 
 class _AE(torch.nn.Module):

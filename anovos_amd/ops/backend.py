@@ -4,8 +4,8 @@ Policy: on a GPU (ROCm) the hand-written gfx950 HIP extension MUST load —
 ops raise loudly if it is missing (no silent eager fallback; set
 ANOVOS_AMD_ALLOW_TORCH_FALLBACK=1 to override for debugging). On CPU the
 torch reference implementations run (CI container has no GPU). Library
-GEMMs (correlation fallback, PCA projection) intentionally go through
-rocBLAS via torch.matmul — that is the sanctioned library path; the fused
+GEMMs (correlation fallback, PCA projection of frames wider than the K27
+kernel takes) intentionally go through rocBLAS via torch.matmul — that is the sanctioned library path; the fused
 kernels in ops/hip/ cover the bespoke hot ops.
 """
 

@@ -1,7 +1,7 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
-// pairwise_gram.hip, row_quadform.hip). Compiled by torch.utils.cpp_extension
-// with hipcc for gfx950; streams come from the caller's current torch HIP
+// pairwise_gram.hip, row_quadform.hip, project_columns.hip). Compiled by
+// torch.utils.cpp_extension with hipcc for gfx950; streams come from the caller's current torch HIP
 // stream so kernels compose with the engine's side-stream overlap
 // (core/dist.py SideStream).
 //
@@ -797,6 +797,68 @@ torch::Tensor row_quadform_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor
   return out;
 }
 
+// K27: the scores y_c = sum_j W[c][j] z_j themselves, z as in K26, as r
+// separate contiguous f32 columns (project_columns.hip). `outs`, if given,
+// are the r columns to write: dense f32 of length n whose first element is
+// 16-byte aligned (the kernel stores four rows at a time; its 16-byte loads
+// of the input columns, like K26's, are legal at any 4-byte alignment, only
+// slower off a 16-byte boundary, so the inputs are not checked). One launch per
+// window of W's rows that fits in LDS; windows write disjoint columns.
+std::vector<torch::Tensor> project_columns_bf16x2(
+    std::vector<torch::Tensor> cols, torch::Tensor shift, torch::Tensor scale, torch::Tensor W,
+    std::optional<std::vector<torch::Tensor>> outs) {
+  ColumnBatch b = gather_columns(cols, "project_columns_bf16x2", F32, /*equal_len=*/true);
+  check_count((size_t)shift.numel(), cols.size(), b.name, "shift");
+  check_count((size_t)scale.numel(), cols.size(), b.name, "scale");
+  TORCH_CHECK(W.dim() == 2 && W.scalar_type() == torch::kFloat32 && W.is_contiguous(), b.name,
+              ": W must be a dense 2-D float32 tensor");
+  const int64_t k = b.ncols();
+  const int64_t r = W.size(0);
+  TORCH_CHECK(W.size(1) == k, b.name, ": W has ", W.size(1), " columns, expected ", k);
+  TORCH_CHECK(k <= ROWQUAD_MAX_COLS, b.name, ": ", k, " columns, at most ", ROWQUAD_MAX_COLS,
+              " (ROWQUAD_MAX_COLS)");
+  TORCH_CHECK(r >= 1 && r <= k, b.name, ": W has ", r, " rows, expected 1 .. ", k);
+  TORCH_CHECK(shift.device() == b.device && scale.device() == b.device && W.device() == b.device,
+              b.name, ": shift, scale and W must be on the columns' device");
+  auto device = b.device;
+  const int64_t n = b.maxn;
+  std::vector<torch::Tensor> res;
+  if (outs) {
+    check_count(outs->size(), (size_t)r, b.name, "outs");
+    for (auto &t : *outs) {
+      check_dense_on_device(t, b, "outs", torch::kFloat32, n);
+      TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, b.name,
+                  ": outs must start at a 16-byte aligned address");
+    }
+    res = *outs;
+  } else {
+    for (int64_t c = 0; c < r; ++c) res.push_back(torch::empty({n}, on(device, torch::kFloat32)));
+  }
+  if (n == 0) return res;
+  auto shift_d = shift.to(torch::kFloat32).contiguous();
+  auto scale_d = scale.to(torch::kFloat32).contiguous();
+  const int r_pad = rowquad_rpad((int)r), k_pad = rowquad_kpad((int)k);
+  auto wimg = torch::empty({2 * (int64_t)(k_pad / 8) * r_pad * 8}, on(device, torch::kInt16));
+  auto dptr = upload(b.ptrs, device);
+  std::vector<int64_t> optrs;
+  for (auto &t : res) optrs.push_back((int64_t)t.data_ptr());
+  auto dout = upload(optrs, device);
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_PROJECT_BLOCKS")) blocks = atoi(e);
+  check_hip(anovos_row_quadform_split(W.data_ptr<float>(), (int)r, (int)k,
+                                      (uint16_t *)wimg.data_ptr<int16_t>(), current_stream()),
+            "anovos_row_quadform_split");
+  const int window = std::min(rowquad_window_rows((int)k), r_pad);
+  for (int r0 = 0; r0 < r_pad; r0 += window)
+    check_hip(anovos_project_columns(ptr_table<const void>(dptr), n, (int)k,
+                                     shift_d.data_ptr<float>(), scale_d.data_ptr<float>(),
+                                     (const uint16_t *)wimg.data_ptr<int16_t>(), (int)r, r0,
+                                     std::min(window, r_pad - r0), blocks, ptr_table<float>(dout),
+                                     current_stream()),
+              "anovos_project_columns");
+  return res;
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1461,6 +1523,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 MFMA pairwise-complete sums [4, k, k] = (N, P, S, Q) (K25)");
   m.def("row_quadform_bf16x2", &row_quadform_bf16x2,
         "per-row |W z|^2 of standardized columns, split-bf16 MFMA (K26)");
+  m.def("project_columns_bf16x2", &project_columns_bf16x2,
+        "scores W z of standardized columns as r separate f32 columns, split-bf16 MFMA (K27)",
+        py::arg("cols"), py::arg("shift"), py::arg("scale"), py::arg("W"),
+        py::arg("outs") = py::none());
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

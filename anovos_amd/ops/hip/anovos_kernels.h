@@ -2,7 +2,8 @@
 //
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
-// grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip):
+// grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip,
+// project_columns.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -82,6 +83,11 @@ __host__ __device__ constexpr int rowquad_window_rows(int k) {
 }
 static_assert(rowquad_window_rows(160) >= 160, "the 150-column benchmark frame takes one launch");
 static_assert(rowquad_window_rows(ROWQUAD_MAX_COLS) >= 16, "a window holds at least one tile");
+// K27 shares K26's column limit, slab, LDS images and window plan. Most
+// components of one launch: a lane keeps three output pointers, one per 64
+// components (project_columns.hip). A window is at most min(r_pad,
+// rowquad_window_rows(k)) <= 160 components.
+constexpr int PROJ_MAX_WINDOW = 192;
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -236,4 +242,10 @@ int anovos_row_quadform_split(const float *W, int r, int k, uint16_t *wimg, hipS
 int anovos_row_quadform(const void *const *cols, int64_t n, int k, const float *shift,
                         const float *scale, const uint16_t *wimg, int r, int r0, int rw_pad,
                         int accumulate, int blocks, float *out, hipStream_t stream);
+// project_columns.hip: the scores themselves. wimg as above; one launch
+// writes the components [r0, min(r0 + rw_pad, r)) of every row into the
+// columns outs[c] (r device pointers, each n floats, 16-byte aligned).
+int anovos_project_columns(const void *const *cols, int64_t n, int k, const float *shift,
+                           const float *scale, const uint16_t *wimg, int r, int r0, int rw_pad,
+                           int blocks, float *const *outs, hipStream_t stream);
 }
