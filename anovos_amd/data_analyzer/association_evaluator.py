@@ -41,7 +41,7 @@ from anovos_amd.shared.tracing import traced
 
 
 @traced
-def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=False, sample_size=1000000, print_impact=False, use_bf16=True, method="pearson", rank_cells=1024, null_policy="mean", min_periods=2):
+def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=False, sample_size=1000000, print_impact=False, use_bf16=True, method="pearson", rank_cells=1024, null_policy="mean", min_periods=2, precision=None):
     """[attribute, <cols...>] — reference association_evaluator.py:38-139.
 
     use_bf16=True (default) runs the hand-written bf16 MFMA Gram kernel:
@@ -71,7 +71,15 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
     values or where either column is constant on those rows (see
     ops/corr.py for the thresholds); `pairwise_observation_counts` returns
     the row count behind each entry. Pearson only: Spearman ranks would
-    have to be retaken per pair."""
+    have to be retaken per pair.
+
+    precision="bf16x2" (method="pearson", null_policy="mean" only) takes the
+    Gram matrix from the split-bf16 kernel K28 and normalises it in fp64:
+    entries within about 2e-5 of the fp64 result where use_bf16=True gives
+    1e-2, at no frame-sized allocation; "fp64" is the library matmul on a
+    centred fp64 copy. None (default) leaves the choice to use_bf16."""
+    if precision is not None and (method != "pearson" or null_policy != "mean"):
+        raise TypeError("Invalid input for precision: only with method='pearson' and null_policy='mean'")
     if method not in ("pearson", "spearman"):
         raise TypeError("Invalid input for method: 'pearson' or 'spearman'")
     if null_policy not in ("mean", "pairwise"):
@@ -104,7 +112,7 @@ def correlation_matrix(ctx, idf, list_of_cols="all", drop_cols=[], use_sampling=
     elif null_policy == "pairwise":
         corr = corr_ops.pairwise_pearson_matrix(idf, cols, use_bf16=use_bf16, min_periods=int(min_periods))
     else:
-        corr = corr_ops.pearson_matrix(idf, cols, use_bf16=use_bf16)
+        corr = corr_ops.pearson_matrix(idf, cols, use_bf16=use_bf16, precision=precision)
     odf = pd.DataFrame(corr, columns=cols, index=cols)
     odf["attribute"] = odf.index
     sorted_cols = sorted(cols)

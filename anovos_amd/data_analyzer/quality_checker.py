@@ -533,6 +533,7 @@ def multivariate_outlier_detection(
     model_path="NA",
     sample_size=1000000,
     print_impact=False,
+    fit_precision="fp64",
 ):
     """Beyond the reference (whose outlier_detection is univariate): rows
     whose combination of values is improbable although every coordinate
@@ -544,7 +545,11 @@ def multivariate_outlier_detection(
     fitted on a sample of `sample_size` rows when the frame is larger; the
     distance is always taken on the full frame. A null counts as the
     column mean. treatment=True removes the flagged rows;
-    append_distance=True appends d2 as the f32 column `distance_col`."""
+    append_distance=True appends d2 as the f32 column `distance_col`.
+    fit_precision="bf16x2" fits the model on the split-bf16 Gram kernel K28
+    (no frame-sized allocation); the eigenvalue floor is then
+    max(rank_tol, k * gamma) (ops/mahalanobis.py) and is reported as the
+    stats row `eigenvalue_floor`."""
     from anovos_amd.ops import mahalanobis as maha_ops
 
     num_cols = attributeType_segregation(idf)[0]
@@ -564,6 +569,8 @@ def multivariate_outlier_detection(
         raise TypeError("Invalid input for threshold: a positive number")
     if isinstance(rank_tol, bool) or not isinstance(rank_tol, (int, float)) or not 0 <= rank_tol < 1:
         raise TypeError("Invalid input for rank_tol: a value in [0, 1)")
+    if fit_precision not in ("fp64", "bf16x2"):
+        raise ValueError("Invalid input for fit_precision: 'fp64' or 'bf16x2'")
     if append_distance and distance_col in idf.columns:
         raise TypeError(f"Invalid input for distance_col: column '{distance_col}' already exists")
 
@@ -600,7 +607,7 @@ def multivariate_outlier_detection(
             idf_sample = data_sample(idf.select(list_of_cols), fraction=sample_size / idf_count, method_type="random", seed_value=11)
         else:
             idf_sample = idf.select(list_of_cols)
-        model = maha_ops.fit_whitening(idf_sample, list_of_cols, rank_tol=rank_tol)
+        model = maha_ops.fit_whitening(idf_sample, list_of_cols, rank_tol=rank_tol, precision=fit_precision)
         model_threshold = None
     if len(model.columns) < 2 or model.rank < 1:
         raise TypeError("Invalid input for Column(s): fewer than 2 numerical columns with a non-zero variance")
@@ -663,6 +670,8 @@ def multivariate_outlier_detection(
         ],
         columns=["metric", "value"],
     )
+    if fit_precision != "fp64" and not pre_existing_model:
+        odf_print.loc[len(odf_print)] = ["eigenvalue_floor", float(model.floor)]
     if print_impact:
         print(odf_print.to_string(index=False))
     return odf, odf_print

@@ -387,6 +387,7 @@ def PCA_latentFeatures(
     root_path="",
     auth_key="NA",
     print_impact=False,
+    fit_precision="fp64",
 ):
     """PCA with k chosen by explained-variance cutoff — reference
     transformers.py:2915-3168. Covariance in fp64, driver eigh, scores from
@@ -397,7 +398,10 @@ def PCA_latentFeatures(
     standardization_configs holds no key besides pre_existing_model and
     model_path and the frame has at most 256 columns; otherwise, as with
     output_mode="append" or imputation=True, z_standardization runs first
-    and its output (one more frame-sized allocation) is projected."""
+    and its output (one more frame-sized allocation) is projected.
+    fit_precision="bf16x2" takes the covariance from the split-bf16 Gram
+    kernel K28 (ops/corr.covariance_matrix) instead of an fp64 copy of the
+    frame: with it a fresh fused fit allocates nothing of frame size."""
     from anovos_amd.data_transformer import transformers as T
     from anovos_amd.ops import corr as corr_ops
     from anovos_amd.ops import project as project_ops
@@ -436,7 +440,7 @@ def PCA_latentFeatures(
         W = np.ascontiguousarray(comp.values, dtype=np.float32)  # [columns, k]
         k = W.shape[1]
     else:
-        cov = corr_ops.covariance_matrix(work, cols, moments=moments)
+        cov = corr_ops.covariance_matrix(work, cols, moments=moments, precision=fit_precision)
         if fused:  # of the standardized columns: D cov D, D = diag(scale)
             cov = cov * np.outer(scale, scale)
         vals, vecs = np.linalg.eigh(cov)

@@ -10,6 +10,10 @@ matrix X^T X of the (mean-centered) column block:
   partial Gram matrices merged with one RCCL all-reduce.
 - Library path (sanctioned): torch.matmul (rocBLAS) on the centered
   block, also the CPU backend.
+- precision="bf16x2" (covariance_matrix, pearson_matrix): the split-bf16
+  Gram kernel K28 (ops/hip/split_gram.hip), hi + lo operands, fp32 chains
+  of SPLITGRAM_FLUSH_ROWS rows flushed into fp64 - accurate enough to fit a
+  whitening or a PCA model on, with no frame-sized allocation.
 
 Null handling matches the reference: correlation_matrix is run on an
 imputed frame (workflow imputes MMM first); any remaining NaN is treated
@@ -33,15 +37,29 @@ from anovos_amd.ops import backend
 from anovos_amd.ops import stats as stats_ops
 
 
-def pearson_matrix(idf, cols: List[str], moments=None, use_bf16: bool = True) -> np.ndarray:
-    """Global Pearson correlation matrix over numeric columns."""
+def pearson_matrix(idf, cols: List[str], moments=None, use_bf16: bool = True,
+                   precision=None) -> np.ndarray:
+    """Global Pearson correlation matrix over numeric columns.
+    precision=None: the bf16 kernel K8 or, with use_bf16=False, an f32
+    library matmul. precision="bf16x2": the split-bf16 Gram of K28
+    normalised in fp64 (the fp64 matmul on the CPU backend);
+    precision="fp64": the fp64 matmul everywhere."""
+    _check_precision(precision, allow_none=True)
     if moments is None:
         moments = stats_ops.frame_moments(idf, cols)
     dev = idf.device
     n = idf.count()
     tensors = [idf.col(c).data for c in cols]
     col_means = [m if m == m else 0.0 for m in (moments[c].mean for c in cols)]
-    if dev.type == "cuda" and backend.use_hip(tensors[0]) and use_bf16:
+    if precision == "bf16x2" and _on_hip(idf, cols):
+        gram = _split_gram(idf, cols, col_means)
+    elif precision is not None:
+        X = torch.stack(
+            [torch.nan_to_num(t.to(torch.float64) - m, nan=0.0) for t, m in zip(tensors, col_means)],
+            dim=1,
+        )
+        gram = X.T @ X
+    elif dev.type == "cuda" and backend.use_hip(tensors[0]) and use_bf16:
         ext = backend.hip_ext()
         # f32 columns: the kernel centers in-register (subtraction of
         # nearby f32 values is exact, error = storage quantization).
@@ -205,19 +223,73 @@ def pairwise_pearson_matrix(idf, cols: List[str], moments=None, use_bf16: bool =
     return r
 
 
-def covariance_matrix(idf, cols: List[str], moments=None) -> np.ndarray:
+# K28 (ops/hip/split_gram.hip): rows one fp32 accumulator takes before it is
+# flushed into fp64 - SPLITGRAM_FLUSH_ROWS of ops/hip/anovos_kernels.h - and
+# the kernel's bound per entry of the Gram matrix, relative to
+# sum |z_i| |z_j| (<= 1 on a correlation matrix): operand split and dropped
+# lo x lo term, the fp32 chain, the two centrings.
+SPLITGRAM_FLUSH_ROWS = 64
+SPLITGRAM_GAMMA = 3 * 2.0 ** -18 + (3 * SPLITGRAM_FLUSH_ROWS + 4) * 2.0 ** -24
+
+PRECISIONS = ("fp64", "bf16x2")
+
+
+def _check_precision(precision, allow_none=False):
+    if precision is None and allow_none:
+        return
+    if precision not in PRECISIONS:
+        raise ValueError(f"Invalid input for precision: one of {PRECISIONS}, got {precision!r}")
+
+
+def _split_gram(idf, cols, col_means) -> torch.Tensor:
+    """Centred Gram matrix of this shard from K28, fp64 [k, k] on the
+    device. f32 columns go in as they are, with their fp64 mean; an f64
+    column is centred in fp64 before the downcast (one column-sized
+    temporary at a time besides the downcast columns themselves)."""
+    ext = backend.hip_ext()
+    if ext.SPLITGRAM_FLUSH_ROWS != SPLITGRAM_FLUSH_ROWS:
+        raise RuntimeError("SPLITGRAM_FLUSH_ROWS of the extension and of ops/corr.py differ")
+    f32, kmeans = [], []
+    for c, m in zip(cols, col_means):
+        t = idf.col(c).data
+        if t.dtype == torch.float32:
+            f32.append(t.contiguous())
+            kmeans.append(m)
+        else:
+            f32.append((t.to(torch.float64) - m).to(torch.float32).contiguous())
+            kmeans.append(0.0)
+    means = torch.tensor(kmeans, dtype=torch.float64).to(idf.device)
+    return ext.centered_gram_bf16x2(f32, means)
+
+
+def _on_hip(idf, cols) -> bool:
+    return idf.device.type == "cuda" and backend.use_hip(idf.col(cols[0]).data)
+
+
+def covariance_matrix(idf, cols: List[str], moments=None, precision: str = "fp64") -> np.ndarray:
     """Global covariance matrix (n-1 denominator, Spark RowMatrix
-    computeCovariance semantics — reference association_eval_varclus.py:71-84)."""
+    computeCovariance semantics — reference association_eval_varclus.py:71-84).
+
+    precision="fp64" stacks a centred fp64 copy of the columns and multiplies
+    it with a library matmul. precision="bf16x2" on the HIP backend takes the
+    Gram matrix from K28 instead - one read of the frame per 64-column group,
+    no frame-sized allocation, every entry within SPLITGRAM_GAMMA *
+    sum |z_i| |z_j| of the fp64 sum; on the CPU backend it runs the fp64
+    code."""
+    _check_precision(precision)
     if moments is None:
         moments = stats_ops.frame_moments(idf, cols)
-    tensors = [idf.col(c).data for c in cols]
     col_means = [m if m == m else 0.0 for m in (moments[c].mean for c in cols)]
-    # center in f64 before any precision loss; NaN contributes zero
-    Xc = torch.stack(
-        [torch.nan_to_num(t.to(torch.float64) - m, nan=0.0) for t, m in zip(tensors, col_means)],
-        dim=1,
-    )
-    gram = Xc.T @ Xc
+    if precision == "bf16x2" and _on_hip(idf, cols):
+        gram = _split_gram(idf, cols, col_means)
+    else:
+        tensors = [idf.col(c).data for c in cols]
+        # center in f64 before any precision loss; NaN contributes zero
+        Xc = torch.stack(
+            [torch.nan_to_num(t.to(torch.float64) - m, nan=0.0) for t, m in zip(tensors, col_means)],
+            dim=1,
+        )
+        gram = Xc.T @ Xc
     if dist.is_dist():
         dist.all_reduce_(gram, "sum")
     n = idf.count()

@@ -1,8 +1,9 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
-// pairwise_gram.hip, row_quadform.hip, project_columns.hip). Compiled by
-// torch.utils.cpp_extension with hipcc for gfx950; streams come from the caller's current torch HIP
-// stream so kernels compose with the engine's side-stream overlap
+// pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip).
+// Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
+// from the caller's current torch HIP stream so kernels compose with the
+// engine's side-stream overlap
 // (core/dist.py SideStream).
 //
 // Every binding has the same shape: gather_columns() validates the column
@@ -748,6 +749,71 @@ torch::Tensor pairwise_gram_bf16(std::vector<torch::Tensor> cols, torch::Tensor 
                                    row_chunks, partials.data_ptr<float>(),
                                    out.data_ptr<double>(), current_stream()),
               "anovos_pairwise_gram");
+  }
+  return out;
+}
+
+// K28: centred Gram matrix G[i][j] = sum z_i z_j, z = isnan(x) ? 0 : x - mean,
+// fp64 [k, k], from split-bf16 MFMA products with fp32 chains of at most
+// SPLITGRAM_FLUSH_ROWS rows flushed into fp64 (split_gram.hip). `means` is
+// taken in fp64 and split into two floats here. Any k: the host loops over
+// the items one wave of blocks holds.
+torch::Tensor centered_gram_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor means) {
+  ColumnBatch b = gather_columns(cols, "centered_gram_bf16x2", F32, /*equal_len=*/true);
+  check_count((size_t)means.numel(), cols.size(), b.name, "means");
+  TORCH_CHECK(means.is_floating_point(), b.name, ": means must be a floating-point tensor");
+  TORCH_CHECK(means.device() == b.device, b.name, ": means must be on the columns' device");
+  auto device = b.device;
+  const int k = b.ncols();
+  const int64_t n = b.maxn;
+  auto out = torch::zeros({k, k}, on(device, torch::kFloat64));
+  if (n == 0) return out;
+  // mh = f32(mean), ml = f32(mean - mh)
+  auto mean64 = means.to(torch::kFloat64).reshape({-1});
+  auto mean_hi = mean64.to(torch::kFloat32);
+  auto mean_lo = (mean64 - mean_hi.to(torch::kFloat64)).to(torch::kFloat32);
+  const int groups = (k + 16 * SPLITGRAM_GROUP_TILES - 1) / (16 * SPLITGRAM_GROUP_TILES);
+  std::vector<int> gi_h, gj_h;
+  for (int i = 0; i < groups; ++i)
+    for (int j = i; j < groups; ++j) {
+      gi_h.push_back(i);
+      gj_h.push_back(j);
+    }
+  const int64_t nitems = (int64_t)gi_h.size();
+  // Row split: one wave of resident blocks over all items, at most one
+  // macro-slab per block. fp64 partials put no limit on a block's rows.
+  const int64_t macro_total = (n + SPLITGRAM_SLAB_ROWS - 1) / SPLITGRAM_SLAB_ROWS;
+  const int64_t capacity = std::max(1, anovos_split_gram_grid());
+  int64_t target_chunks = std::max<int64_t>(1, capacity / nitems);
+  if (const char *e = getenv("ANOVOS_SPLITGRAM_CHUNKS")) target_chunks = atoll(e);
+  const int row_chunks =
+      (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(target_chunks, macro_total),
+                                                  INT32_MAX / SPLITGRAM_ITEM_DOUBLES));
+  // Measurement only (tools/bench_covariance.py): rows per fp32 chain. A
+  // value above SPLITGRAM_FLUSH_ROWS widens the error bound accordingly.
+  int64_t flush_rows = SPLITGRAM_FLUSH_ROWS;
+  if (const char *e = getenv("ANOVOS_SPLITGRAM_FLUSH_ROWS")) flush_rows = atoll(e);
+  TORCH_CHECK(flush_rows >= SPLITGRAM_SLAB_ROWS && flush_rows % SPLITGRAM_SLAB_ROWS == 0 &&
+                  flush_rows <= (1 << 20),
+              b.name, ": ANOVOS_SPLITGRAM_FLUSH_ROWS must be a multiple of ", SPLITGRAM_SLAB_ROWS,
+              " in [", SPLITGRAM_SLAB_ROWS, ", 2^20]");
+  // Items per launch: what one wave of blocks holds, so that the partials
+  // stay bounded however many groups k makes.
+  const int64_t per_launch = std::max<int64_t>(1, std::min(nitems, capacity / row_chunks));
+  auto gi = upload(gi_h, device);
+  auto gj = upload(gj_h, device);
+  auto dptr = upload(b.ptrs, device);
+  auto partials = torch::empty({(int64_t)row_chunks * per_launch, SPLITGRAM_ITEM_DOUBLES},
+                               on(device, torch::kFloat64));
+  for (int64_t item0 = 0; item0 < nitems; item0 += per_launch) {
+    const int cnt = (int)std::min(per_launch, nitems - item0);
+    check_hip(anovos_split_gram(ptr_table<const void>(dptr), n, k, mean_hi.data_ptr<float>(),
+                                mean_lo.data_ptr<float>(), gi.data_ptr<int>() + item0,
+                                gj.data_ptr<int>() + item0, cnt, row_chunks,
+                                (int)(flush_rows / SPLITGRAM_SLAB_ROWS),
+                                partials.data_ptr<double>(), out.data_ptr<double>(),
+                                current_stream()),
+              "anovos_split_gram");
   }
   return out;
 }
@@ -1521,6 +1587,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("centered_gram_bf16", &centered_gram_bf16, "bf16 MFMA centered Gram X^T X (K8)");
   m.def("pairwise_gram_bf16", &pairwise_gram_bf16,
         "bf16 MFMA pairwise-complete sums [4, k, k] = (N, P, S, Q) (K25)");
+  m.def("centered_gram_bf16x2", &centered_gram_bf16x2,
+        "split-bf16 MFMA centred Gram X^T X, fp32 chains flushed into fp64, fp64 [k, k] (K28)");
+  m.attr("SPLITGRAM_FLUSH_ROWS") = SPLITGRAM_FLUSH_ROWS;
   m.def("row_quadform_bf16x2", &row_quadform_bf16x2,
         "per-row |W z|^2 of standardized columns, split-bf16 MFMA (K26)");
   m.def("project_columns_bf16x2", &project_columns_bf16x2,

@@ -3,7 +3,7 @@
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
 // grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip,
-// project_columns.hip):
+// project_columns.hip, split_gram.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -88,6 +88,16 @@ static_assert(rowquad_window_rows(ROWQUAD_MAX_COLS) >= 16, "a window holds at le
 // components (project_columns.hip). A window is at most min(r_pad,
 // rowquad_window_rows(k)) <= 160 components.
 constexpr int PROJ_MAX_WINDOW = 192;
+// K28: tiles per column group and rows of a macro-slab as K25; fp64 partials
+// one block writes (tile pairs x 256); and the rows whose products one fp32
+// accumulator takes before it is added into its fp64 shadow - a multiple of
+// the macro-slab. The kernel's per-entry error bound on sum |z_i| |z_j|,
+//   3 * 2^-18 + (3 * SPLITGRAM_FLUSH_ROWS + 4) * 2^-24,
+// depends on it (ops/corr.py SPLITGRAM_GAMMA repeats the figure).
+constexpr int SPLITGRAM_GROUP_TILES = 4;
+constexpr int SPLITGRAM_SLAB_ROWS = 64;
+constexpr int SPLITGRAM_ITEM_DOUBLES = SPLITGRAM_GROUP_TILES * SPLITGRAM_GROUP_TILES * 256;
+constexpr int SPLITGRAM_FLUSH_ROWS = 64;
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -232,6 +242,15 @@ int anovos_pairwise_gram(const void *const *cols, int64_t n, int k, const float 
                          const int *item_gi, const int *item_gj, int nitems, int row_chunks,
                          float *partials, double *out, hipStream_t stream);
 int anovos_pairwise_gram_grid();
+// split_gram.hip: out is fp64 [k, k]; mean_hi + mean_lo is the fp64 mean
+// split into two floats; items as above; an fp32 accumulator is flushed
+// into fp64 every flush_slabs macro-slabs; partials holds
+// row_chunks * nitems * SPLITGRAM_ITEM_DOUBLES doubles. n >= 1.
+int anovos_split_gram(const void *const *cols, int64_t n, int k, const float *mean_hi,
+                      const float *mean_lo, const int *item_gi, const int *item_gj, int nitems,
+                      int row_chunks, int flush_slabs, double *partials, double *out,
+                      hipStream_t stream);
+int anovos_split_gram_grid();
 // row_quadform.hip: wimg holds the two bf16 planes of W [r, k] as
 // 2 * (k_pad / 8) * r_pad * 8 uint16 (anovos_row_quadform_split fills it,
 // once per call); one launch takes the rows [r0, r0 + rw_pad) of it, both

@@ -19,6 +19,12 @@ spectrum free of the columns' scales.
 
 - fit_whitening: mu, sd, W, r from ops/corr.covariance_matrix (fp64, one
   all-reduce under torch.distributed, so every rank gets the same model).
+  precision="bf16x2" takes the covariance from the split-bf16 Gram kernel
+  K28 instead, with no frame-sized allocation; its per-entry error bound
+  gamma (corr.SPLITGRAM_GAMMA) on a correlation matrix moves no eigenvalue
+  by more than k * gamma * lambda_max (Weyl, with |E|_2 <= k max |E_ij|), so
+  the eigenvalue floor becomes max(rank_tol, k * gamma): below it a kept
+  eigenvalue could be rounding alone. The floor in use is `model.floor`.
 - mahalanobis_d2: per-row f32 tensor. HIP path (ops/hip/row_quadform.hip):
   split-bf16 MFMA, three products, fp32 accumulation. CPU backend: fp64
   torch in row slabs.
@@ -55,6 +61,7 @@ class WhiteningModel:
     W: np.ndarray               # [r, k] fp64
     rank: int
     excluded: List[str] = field(default_factory=list)  # zero / non-finite variance
+    floor: float = 1e-6         # eigenvalues kept lie above floor * lambda_max
 
 
 def whitening_from_covariance(cov: np.ndarray, rank_tol: float = 1e-6):
@@ -73,14 +80,24 @@ def whitening_from_covariance(cov: np.ndarray, rank_tol: float = 1e-6):
     return sd, np.ascontiguousarray(W), int(lam.size)
 
 
-def fit_whitening(idf, cols: List[str], moments=None, rank_tol: float = 1e-6) -> WhiteningModel:
+def eigen_floor(k: int, rank_tol: float, precision: str) -> float:
+    """Relative eigenvalue floor of a k-column fit at `precision`."""
+    if precision == "bf16x2":
+        return max(float(rank_tol), k * corr_ops.SPLITGRAM_GAMMA)
+    return float(rank_tol)
+
+
+def fit_whitening(idf, cols: List[str], moments=None, rank_tol: float = 1e-6,
+                  precision: str = "fp64") -> WhiteningModel:
     """Means, standard deviations (ddof = 1) and the whitening matrix of the
     columns. Columns with zero or non-finite variance are left out of the
-    model and listed in `excluded`."""
+    model and listed in `excluded`. `precision` is covariance_matrix's; the
+    floor follows from it (eigen_floor) on every backend, so a model does
+    not depend on where it was fitted."""
     cols = list(cols)
     if moments is None:
         moments = stats_ops.frame_moments(idf, cols)
-    cov = corr_ops.covariance_matrix(idf, cols, moments=moments)
+    cov = corr_ops.covariance_matrix(idf, cols, moments=moments, precision=precision)
     var = np.diag(cov)
     ok = np.isfinite(var) & (var > 0)
     # a column without a finite mean (all null) has no finite variance either
@@ -89,12 +106,13 @@ def fit_whitening(idf, cols: List[str], moments=None, rank_tol: float = 1e-6) ->
     excluded = [c for c, g in zip(cols, ok) if not g]
     mean = np.array([moments[c].mean for c in used], dtype=np.float64)
     if len(used) < 1:
-        return WhiteningModel(used, mean, np.zeros(0), np.zeros((0, 0)), 0, excluded)
+        return WhiteningModel(used, mean, np.zeros(0), np.zeros((0, 0)), 0, excluded, float(rank_tol))
     sub = cov[np.ix_(ok, ok)]
     if not np.all(np.isfinite(sub)):
         raise ValueError("fit_whitening: covariance matrix is not finite")
-    sd, W, r = whitening_from_covariance(sub, rank_tol)
-    return WhiteningModel(used, mean, sd, W, r, excluded)
+    floor = eigen_floor(len(used), rank_tol, precision)
+    sd, W, r = whitening_from_covariance(sub, floor)
+    return WhiteningModel(used, mean, sd, W, r, excluded, floor)
 
 
 def mahalanobis_d2(idf, cols: List[str], model: WhiteningModel) -> torch.Tensor:
