@@ -28,6 +28,7 @@ import torch
 
 from anovos_amd.core import dist
 from anovos_amd.core.frame import AnovosFrame, Column
+from anovos_amd.ops import knn as knn_ops
 from anovos_amd.ops import stats as stats_ops
 from anovos_amd.shared.utils import attributeType_segregation, normalize_columns
 
@@ -75,13 +76,21 @@ def imputation_sklearn(
     run_type="local",
     auth_key="NA",
     print_impact=False,
+    apply_precision="fp64",
 ):
-    """KNN / IterativeImputer(regression) — reference transformers.py:1677-2020."""
+    """KNN / IterativeImputer(regression) — reference transformers.py:1677-2020.
+
+    apply_precision (KNN only; ignored for regression): "fp64" applies the
+    model with fp64 torch GEMMs; "bf16x2" with the K29 kernel (ops/knn.py) on
+    the HIP backend, where a model within its limits (128 columns, 8
+    neighbours, 65 536 donors) needs no [rows, donors] matrix."""
     from sklearn.experimental import enable_iterative_imputer  # noqa: F401
     from sklearn.impute import IterativeImputer, KNNImputer
 
     if method_type not in ("KNN", "regression"):
         raise TypeError("Invalid input for method_type")
+    if method_type == "KNN":
+        knn_ops.check_apply_precision(apply_precision)
     cols = _resolve_missing_cols(ctx, idf, list_of_cols, drop_cols, stats_missing)
     if not cols:
         warnings.warn("No Imputation performed - No numerical column(s) with missing values")
@@ -118,77 +127,45 @@ def imputation_sklearn(
     # model is re-expressed as tensor ops and applied in GPU batches —
     # only ROWS THAT HAVE a missing value go through the solver.
     dev = idf.device
-    nan_any = torch.zeros(idf.local_rows(), dtype=torch.bool, device=dev)
-    for c in cols:
-        nan_any |= torch.isnan(idf.col(c).data)
-    nan_rows = nan_any.nonzero(as_tuple=True)[0]
+    filled = {}  # column -> (rows, values) of its null entries
+    if method_type == "KNN" and apply_precision == "bf16x2":
+        filled = knn_ops.knn_impute(idf, cols, model._fit_X, int(model.n_neighbors))
+    else:
+        nan_any = torch.zeros(idf.local_rows(), dtype=torch.bool, device=dev)
+        for c in cols:
+            nan_any |= torch.isnan(idf.col(c).data)
+        nan_rows = nan_any.nonzero(as_tuple=True)[0]
+        if nan_rows.numel():
+            # f64 throughout: f32 GEMM distances flip near-tie neighbor
+            # choices vs sklearn's f64 reference
+            B = torch.stack([idf.col(c).data[nan_rows].to(torch.float64) for c in cols], dim=1)
+            if method_type == "KNN":
+                fitted = torch.from_numpy(np.asarray(model._fit_X, dtype=np.float64)).to(dev)
+                filled_B = _knn_impute_batched(B, fitted, int(model.n_neighbors))
+            else:
+                filled_B = _iterative_impute_apply(B, model, dev)
+            for j, c in enumerate(cols):
+                sub_nan = torch.isnan(B[:, j])
+                filled[c] = (nan_rows[sub_nan], filled_B[:, j][sub_nan])
     odf = idf
-    if nan_rows.numel():
-        # f64 throughout: f32 GEMM distances flip near-tie neighbor
-        # choices vs sklearn's f64 reference
-        B = torch.stack([idf.col(c).data[nan_rows].to(torch.float64) for c in cols], dim=1)
-        if method_type == "KNN":
-            fitted = torch.from_numpy(np.asarray(model._fit_X, dtype=np.float64)).to(dev)
-            filled_B = _knn_impute_batched(B, fitted, int(model.n_neighbors))
-        else:
-            filled_B = _iterative_impute_apply(B, model, dev)
-        for j, c in enumerate(cols):
-            col = idf.col(c)
-            data = col.data.clone()
-            sub_nan = torch.isnan(B[:, j])
-            data[nan_rows[sub_nan]] = filled_B[:, j][sub_nan].to(col.data.dtype)
-            name = c if output_mode == "replace" else c + "_imputed"
-            odf = odf.with_column(name, Column(name, col.dtype, data))
-    elif output_mode == "append":
+    if filled or output_mode == "append":
         for c in cols:
             col = idf.col(c)
-            odf = odf.with_column(c + "_imputed", Column(c + "_imputed", col.dtype, col.data.clone()))
+            data = col.data.clone()
+            if c in filled:
+                rows, vals = filled[c]
+                data[rows] = vals.to(col.data.dtype)
+            name = c if output_mode == "replace" else c + "_imputed"
+            odf = odf.with_column(name, Column(name, col.dtype, data))
     if print_impact:
         print(odf.columns)
     return odf
 
 
 def _knn_impute_batched(B: torch.Tensor, F: torch.Tensor, k: int, batch: int = 16384) -> torch.Tensor:
-    """sklearn KNNImputer.transform semantics on device: nan-euclidean
-    distances dist^2 = m/|overlap| * sum_overlap (x-f)^2 via three GEMMs
-    per batch, per-column donor selection (non-missing target, finite
-    distance), uniform-weight mean of the k nearest, column-mean
-    fallback when no donor exists."""
-    m = B.shape[1]
-    Mf = (~torch.isnan(F)).to(F.dtype)
-    Fv = torch.nan_to_num(F)
-    col_mean = Fv.sum(0) / Mf.sum(0).clamp(min=1.0)
-    F2 = (Fv * Fv) * Mf
-    out = B.clone()
-    for s in range(0, B.shape[0], batch):
-        b = B[s : s + batch]
-        Mx = (~torch.isnan(b)).to(b.dtype)
-        Xv = torch.nan_to_num(b)
-        S1 = (Xv * Xv * Mx) @ Mf.T
-        S2 = Mx @ F2.T
-        S3 = (Xv * Mx) @ (Fv * Mf).T
-        overlap = Mx @ Mf.T  # [b, s]
-        sq = (S1 + S2 - 2 * S3).clamp(min=0.0)
-        d2 = torch.where(overlap > 0, m * sq / overlap.clamp(min=1.0), torch.full_like(sq, float("inf")))
-        miss = torch.isnan(b)
-        for j in range(m):
-            rows = miss[:, j].nonzero(as_tuple=True)[0]
-            if not rows.numel():
-                continue
-            # donors: fitted rows with col j present and finite distance
-            dj = d2[rows] + torch.where(Mf[:, j] > 0, torch.zeros(1, device=B.device), torch.full((1,), float("inf"), device=B.device))
-            kk = min(k, int((Mf[:, j] > 0).sum()))
-            if kk == 0:
-                out[s + rows, j] = col_mean[j]
-                continue
-            vals, idx = torch.topk(dj, kk, dim=1, largest=False)
-            donor = Fv[:, j][idx]  # [r, kk]
-            ok = torch.isfinite(vals)
-            cnt = ok.sum(1).clamp(min=1)
-            est = (donor * ok).sum(1) / cnt
-            est = torch.where(ok.any(1), est, col_mean[j].expand_as(est))
-            out[s + rows, j] = est
-    return out
+    """sklearn KNNImputer.transform semantics on device in fp64 torch
+    (ops/knn.py knn_impute_fp64, where the K29 path shares its definition)."""
+    return knn_ops.knn_impute_fp64(B, F, k, batch)
 
 
 def _iterative_impute_apply(B: torch.Tensor, model, dev) -> torch.Tensor:

@@ -1,6 +1,7 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
-// pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip).
+// pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip,
+// knn_impute.hip).
 // Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
 // from the caller's current torch HIP stream so kernels compose with the
 // engine's side-stream overlap
@@ -18,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <optional>
 #include <vector>
 
@@ -925,6 +927,72 @@ std::vector<torch::Tensor> project_columns_bf16x2(
   return res;
 }
 
+// K29: KNN imputation of the rows `rows` (int64 indices, the null rows of
+// column `target`) against the donors [s, m] (knn_impute.hip). `center` [m]
+// is taken as fp64 and split into two floats on the host. Returns
+// (est f32 [r], idx int32 [r, k], d2 f32 [r, k]); a missing neighbour is
+// idx -1 / d2 +inf, est is NaN where a row has no donor. With `candidates`
+// two more follow: (cand_idx int32, cand_d2 f32) [r, 4 * KNN_CAND], every
+// lane's list as the filter pass left it - what the error-bound tests read.
+std::vector<torch::Tensor> knn_impute_bf16x2(
+    std::vector<torch::Tensor> cols, torch::Tensor rows, torch::Tensor center,
+    torch::Tensor donors, int64_t target, int64_t k, bool candidates) {
+  ColumnBatch b = gather_columns(cols, "knn_impute_bf16x2", F32, /*equal_len=*/true);
+  const int64_t m = b.ncols();
+  TORCH_CHECK(m <= KNN_MAX_COLS, b.name, ": ", m, " columns, at most ", KNN_MAX_COLS,
+              " (KNN_MAX_COLS)");
+  TORCH_CHECK(k >= 1 && k <= KNN_MAX_K, b.name, ": k = ", k, ", expected 1 .. ", KNN_MAX_K,
+              " (KNN_MAX_K)");
+  TORCH_CHECK(target >= 0 && target < m, b.name, ": target ", target, " outside the ", m,
+              " columns");
+  TORCH_CHECK(donors.dim() == 2 && donors.size(1) == m, b.name, ": donors must be [s, ", m, "]");
+  check_dense_on_device(donors, b, "donors", torch::kFloat32, donors.numel());
+  const int64_t s = donors.size(0);
+  TORCH_CHECK(s <= KNN_MAX_DONORS, b.name, ": ", s, " donors, at most ", KNN_MAX_DONORS,
+              " (KNN_MAX_DONORS)");
+  TORCH_CHECK(rows.dim() == 1, b.name, ": rows must be 1-D");
+  check_dense_on_device(rows, b, "rows", torch::kInt64, rows.numel());
+  auto ctr = host_f64(center, (size_t)m, b.name, "center");
+  auto device = b.device;
+  const int64_t r = rows.numel();
+  auto est = torch::full({r}, std::numeric_limits<float>::quiet_NaN(), on(device, torch::kFloat32));
+  auto idx = torch::full({r, k}, -1, on(device, torch::kInt32));
+  auto d2 = torch::full({r, k}, std::numeric_limits<float>::infinity(), on(device, torch::kFloat32));
+  std::vector<torch::Tensor> res = {est, idx, d2};
+  if (candidates) {
+    res.push_back(torch::full({r, 4 * KNN_CAND}, -1, on(device, torch::kInt32)));
+    res.push_back(torch::full({r, 4 * KNN_CAND}, std::numeric_limits<float>::infinity(),
+                              on(device, torch::kFloat32)));
+  }
+  if (r == 0 || s == 0 || b.maxn == 0) return res;
+  const int m_pad = knn_mpad((int)m);
+  std::vector<float> mh(m_pad, 0.f), ml(m_pad, 0.f);
+  for (int64_t j = 0; j < m; ++j) {
+    mh[j] = (float)ctr[j];
+    ml[j] = (float)(ctr[j] - (double)mh[j]);
+  }
+  auto mh_d = upload(mh, device), ml_d = upload(ml, device);
+  auto dptr = upload(b.ptrs, device);
+  auto img = torch::empty({(int64_t)knn_tiles((int)s) * knn_tile_shorts((int)m)},
+                          on(device, torch::kInt16));
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_KNN_BLOCKS")) blocks = atoi(e);
+  check_hip(anovos_knn_donor_image(donors.data_ptr<float>(), (int)s, (int)m, (int)target,
+                                   mh_d.data_ptr<float>(), ml_d.data_ptr<float>(),
+                                   (uint16_t *)img.data_ptr<int16_t>(), current_stream()),
+            "anovos_knn_donor_image");
+  check_hip(anovos_knn_impute(ptr_table<const void>(dptr), b.maxn, (int)m,
+                              rows.data_ptr<int64_t>(), r, mh_d.data_ptr<float>(),
+                              ml_d.data_ptr<float>(), donors.data_ptr<float>(), (int)s,
+                              (int)target, (int)k, (const uint16_t *)img.data_ptr<int16_t>(),
+                              blocks, est.data_ptr<float>(), idx.data_ptr<int32_t>(),
+                              d2.data_ptr<float>(),
+                              candidates ? res[3].data_ptr<int32_t>() : nullptr,
+                              candidates ? res[4].data_ptr<float>() : nullptr, current_stream()),
+            "anovos_knn_impute");
+  return res;
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1596,6 +1664,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "scores W z of standardized columns as r separate f32 columns, split-bf16 MFMA (K27)",
         py::arg("cols"), py::arg("shift"), py::arg("scale"), py::arg("W"),
         py::arg("outs") = py::none());
+  m.def("knn_impute_bf16x2", &knn_impute_bf16x2,
+        "KNN imputation of one column's null rows: (est, idx, d2) of the k nearest donors, "
+        "split-bf16 MFMA filter and exact f32 re-rank (K29)",
+        py::arg("cols"), py::arg("rows"), py::arg("center"), py::arg("donors"), py::arg("target"),
+        py::arg("k"), py::arg("candidates") = false);
+  m.attr("KNN_CAND") = KNN_CAND;
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

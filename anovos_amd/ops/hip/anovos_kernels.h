@@ -98,6 +98,32 @@ constexpr int SPLITGRAM_GROUP_TILES = 4;
 constexpr int SPLITGRAM_SLAB_ROWS = 64;
 constexpr int SPLITGRAM_ITEM_DOUBLES = SPLITGRAM_GROUP_TILES * SPLITGRAM_GROUP_TILES * 256;
 constexpr int SPLITGRAM_FLUSH_ROWS = 64;
+// K29: KNN imputation apply (knn_impute.hip). Most columns of a model
+// (m_pad = 32 * KS, KS <= 4), most neighbours, most donors (a donor index
+// and the image offsets stay far below 2^31); rows of the slab a block owns
+// at a time; donor tiles (16 donors each) of one stage of the LDS ring.
+// KNN_CAND: entries of a lane's private candidate list. A lane sees the
+// donors d with (d % 16) / 4 == lane / 16, a quarter of them, and a true
+// neighbour is lost from its list only if KNN_CAND donors of the same
+// quarter look nearer in the filter pass. With KNN_CAND = KNN_MAX_K + 8 that
+// takes k + 8 donors that look nearer overall, so: the k true neighbours
+// survive whenever they are among the k + 8 nearest of the filter pass, and
+// the union of a row's four lists (4 * KNN_CAND = 64 >= k + 8) is what the
+// exact re-rank orders.
+constexpr int KNN_MAX_COLS = 128;
+constexpr int KNN_MAX_K = 8;
+constexpr int KNN_MAX_DONORS = 65536;
+constexpr int KNN_SLAB_ROWS = 64;
+constexpr int KNN_STAGE_TILES = 2;
+constexpr int KNN_CAND = KNN_MAX_K + 8;
+__host__ __device__ constexpr int knn_mpad(int m) { return (m + 31) / 32 * 32; }
+// donor tiles of the image: padded to whole stages
+__host__ __device__ constexpr int knn_tiles(int s) {
+  return ((s + 15) / 16 + KNN_STAGE_TILES - 1) / KNN_STAGE_TILES * KNN_STAGE_TILES;
+}
+// uint16 entries of one donor tile of the image: 5 planes x KS k-steps x 64
+// lanes x 8 columns
+__host__ __device__ constexpr int knn_tile_shorts(int m) { return 5 * (knn_mpad(m) / 32) * 512; }
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -267,4 +293,20 @@ int anovos_row_quadform(const void *const *cols, int64_t n, int k, const float *
 int anovos_project_columns(const void *const *cols, int64_t n, int k, const float *shift,
                            const float *scale, const uint16_t *wimg, int r, int r0, int rw_pad,
                            int blocks, float *const *outs, hipStream_t stream);
+// knn_impute.hip: donors is f32 [s, m] row-major with NaN for null, mean_hi +
+// mean_lo the per-column centre split into two floats (m entries). The
+// image kernel fills img (knn_tiles(s) * knn_tile_shorts(m) uint16) for the
+// target column; the apply kernel takes the r tasks rows[0 .. r) of that
+// column (row indices into the n-row columns cols[0 .. m); an index outside
+// [0, n) counts as a row of nulls) and writes est[r], idx[r, k], d2[r, k].
+// cand_idx / cand_d2, if not null, take [r, 4 * KNN_CAND]: every lane's
+// candidate list as the filter pass left it (donor -1 / +inf where empty).
+// 1 <= m <= KNN_MAX_COLS, 1 <= s <= KNN_MAX_DONORS, 1 <= k <= KNN_MAX_K,
+// r >= 1. blocks <= 0: one wave of resident blocks.
+int anovos_knn_donor_image(const float *donors, int s, int m, int target, const float *mean_hi,
+                           const float *mean_lo, uint16_t *img, hipStream_t stream);
+int anovos_knn_impute(const void *const *cols, int64_t n, int m, const int64_t *rows, int64_t r,
+                      const float *mean_hi, const float *mean_lo, const float *donors, int s,
+                      int target, int k, const uint16_t *img, int blocks, float *est, int *idx,
+                      float *d2, int *cand_idx, float *cand_d2, hipStream_t stream);
 }

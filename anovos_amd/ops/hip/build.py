@@ -33,6 +33,7 @@ def build(verbose: bool = True) -> str:
             os.path.join(HERE, "row_quadform.hip"),
             os.path.join(HERE, "project_columns.hip"),
             os.path.join(HERE, "split_gram.hip"),
+            os.path.join(HERE, "knn_impute.hip"),
         ],
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],
