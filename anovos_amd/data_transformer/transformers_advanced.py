@@ -468,6 +468,19 @@ def _project_library(work, cols, W):
     return outs
 
 
+def _ae_sample(t, idx, shift, scale):
+    """One column of the autoencoder's training sample: the rows `idx` (all
+    if None) as f32, standardized as the K30 kernel does it - an f64 column
+    centred before the downcast - with nulls as 0."""
+    t = t if idx is None else t[idx]
+    if shift != 0.0 or scale != 1.0:
+        if t.dtype == torch.float32:
+            t = (t - torch.tensor(shift, dtype=torch.float64).to(torch.float32)) * torch.tensor(scale, dtype=torch.float64).to(torch.float32)
+        else:
+            t = (t.to(torch.float64) - shift).to(torch.float32) * torch.tensor(scale, dtype=torch.float64).to(torch.float32)
+    return torch.nan_to_num(t.to(torch.float32), nan=0.0)
+
+
 class _AE(torch.nn.Module):
     def __init__(self, d, bottleneck):
         super().__init__()
@@ -500,11 +513,27 @@ def autoencoder_latentFeatures(
     root_path="",
     auth_key="NA",
     print_impact=False,
+    apply_precision="fp32",
 ):
     """MLP autoencoder latent features — reference transformers.py:2524-2913,
     torch-native (the reference uses Keras on the driver; here training
-    and batched inference run on the MI355X)."""
+    and batched inference run on the MI355X).
+    apply_precision="bf16x2" encodes through the fused K30 kernel
+    (ops/mlp.py) instead of three library GEMMs over a stacked copy of the
+    frame: every latent column is a contiguous tensor of its own, and a
+    fresh fit gathers its training sample per column. With
+    output_mode="replace" the standardization is applied inside the kernel
+    (shift = mean, scale = 1 / stddev) and the standardized frame is not
+    materialised - provided standardization_configs holds no key besides
+    pre_existing_model and model_path and the shape is one the kernel takes;
+    otherwise z_standardization runs first. On the CPU backend the values
+    are those of "fp32", bit for bit. The model file is the same either way."""
     from anovos_amd.data_transformer import transformers as T
+    from anovos_amd.ops import backend
+    from anovos_amd.ops import mlp as mlp_ops
+
+    if apply_precision not in ("fp32", "bf16x2"):
+        raise TypeError("Invalid input for apply_precision: 'fp32' or 'bf16x2'")
 
     num_cols = attributeType_segregation(idf)[0]
     if list_of_cols == "all":
@@ -517,18 +546,44 @@ def autoencoder_latentFeatures(
     work = idf
     if imputation:
         work = T.imputation_MMM(ctx, work, cols)
-    if standardization:
-        work = T.z_standardization(ctx, work, cols, **standardization_configs)
     dev = idf.device
-    model = _AE(len(cols), bottleneck).to(dev)
+    d = len(cols)
+    split = apply_precision == "bf16x2"
+    shift = np.zeros(d)
+    scale = np.ones(d)
+    # as in PCA_latentFeatures: the standardization folds into the kernel
+    # where its output is not part of the result and its model is the plain one
+    fused = (
+        split
+        and standardization
+        and output_mode == "replace"
+        and set(standardization_configs) <= {"pre_existing_model", "model_path"}
+        and mlp_ops.kernel_takes(d, (2 * d, max(d // 2, bottleneck), bottleneck))
+        and backend.use_hip(idf.col(cols[0]).data)
+    )
+    if fused:
+        params, excluded, _ = T._z_standardization_params(work, cols, **standardization_configs)
+        for i, c in enumerate(cols):
+            if c not in excluded:
+                shift[i], scale[i] = params[c][0], 1.0 / params[c][1]
+    elif standardization:
+        work = T.z_standardization(ctx, work, cols, **standardization_configs)
+    model = _AE(d, bottleneck).to(dev)
     if pre_existing_model:
         model.load_state_dict(torch.load(os.path.join(model_path, "autoencoder_latentFeatures.pt"), map_location=dev))
     else:
-        X = torch.stack([torch.nan_to_num(work.col(c).data.to(torch.float32), nan=0.0) for c in cols], dim=1)
-        n = X.shape[0]
-        if n > sample_size:
-            idx = torch.randperm(n, device=X.device)[:sample_size]
-            X = X[idx]
+        if split:
+            # sample indices first, then the sample column by column: no
+            # [n, d] block of the frame
+            n = int(work.col(cols[0]).data.shape[0])
+            idx = torch.randperm(n, device=dev)[:sample_size] if n > sample_size else None
+            X = torch.stack([_ae_sample(work.col(c).data, idx, shift[i], scale[i]) for i, c in enumerate(cols)], dim=1)
+        else:
+            X = torch.stack([torch.nan_to_num(work.col(c).data.to(torch.float32), nan=0.0) for c in cols], dim=1)
+            n = X.shape[0]
+            if n > sample_size:
+                idx = torch.randperm(n, device=X.device)[:sample_size]
+                X = X[idx]
         opt = torch.optim.Adam(model.parameters(), lr=1e-3)
         loss_fn = torch.nn.MSELoss()
         model.train()
@@ -544,17 +599,22 @@ def autoencoder_latentFeatures(
             os.makedirs(model_path, exist_ok=True)
             torch.save(model.state_dict(), os.path.join(model_path, "autoencoder_latentFeatures.pt"))
         dist.barrier()
-    model.eval()
-    X = torch.stack([torch.nan_to_num(work.col(c).data.to(torch.float32), nan=0.0) for c in cols], dim=1)
-    outs = []
-    with torch.no_grad():
-        for s in range(0, X.shape[0], 65536):
-            outs.append(model.encoder(X[s : s + 65536]))
-    Z = torch.cat(outs) if outs else torch.zeros(0, bottleneck, device=dev)
+    if split:
+        enc = model.encoder
+        latents = mlp_ops.mlp_encode(work, cols, shift, scale, [(enc[i].weight, enc[i].bias) for i in (0, 2, 4)])
+    else:
+        model.eval()
+        X = torch.stack([torch.nan_to_num(work.col(c).data.to(torch.float32), nan=0.0) for c in cols], dim=1)
+        outs = []
+        with torch.no_grad():
+            for s in range(0, X.shape[0], 65536):
+                outs.append(model.encoder(X[s : s + 65536]))
+        Z = torch.cat(outs) if outs else torch.zeros(0, bottleneck, device=dev)
+        latents = [Z[:, j] for j in range(bottleneck)]
     odf = work
     for j in range(bottleneck):
         name = f"latent_{j}"
-        odf = odf.with_column(name, Column(name, "double", Z[:, j]))
+        odf = odf.with_column(name, Column(name, "double", latents[j]))
     if output_mode == "replace":
         odf = odf.drop(cols)
     if print_impact:

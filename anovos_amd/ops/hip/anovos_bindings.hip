@@ -1,7 +1,7 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
 // pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip,
-// knn_impute.hip).
+// knn_impute.hip, mlp_encode.hip).
 // Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
 // from the caller's current torch HIP stream so kernels compose with the
 // engine's side-stream overlap
@@ -993,6 +993,75 @@ std::vector<torch::Tensor> knn_impute_bf16x2(
   return res;
 }
 
+// K30: y = W3 relu(W2 relu(W1 z + b1) + b2) + b3 of every row, z as in K26,
+// as n3 separate contiguous f32 columns (mlp_encode.hip). Weights are f32
+// row-major as torch.nn.Linear stores them. `outs` as in K27: dense f32 of
+// length n whose first element is 16-byte aligned.
+std::vector<torch::Tensor> mlp_encode_bf16x2(
+    std::vector<torch::Tensor> cols, torch::Tensor shift, torch::Tensor scale, torch::Tensor W1,
+    torch::Tensor b1, torch::Tensor W2, torch::Tensor b2, torch::Tensor W3, torch::Tensor b3,
+    std::optional<std::vector<torch::Tensor>> outs) {
+  ColumnBatch b = gather_columns(cols, "mlp_encode_bf16x2", F32, /*equal_len=*/true);
+  check_count((size_t)shift.numel(), cols.size(), b.name, "shift");
+  check_count((size_t)scale.numel(), cols.size(), b.name, "scale");
+  const int64_t d = b.ncols();
+  TORCH_CHECK(d <= MLP_MAX_COLS, b.name, ": ", d, " columns, at most ", MLP_MAX_COLS,
+              " (MLP_MAX_COLS)");
+  const torch::Tensor *Ws[3] = {&W1, &W2, &W3}, *bs[3] = {&b1, &b2, &b3};
+  int64_t width[4] = {d, 0, 0, 0};
+  for (int l = 0; l < 3; ++l) {
+    const auto &W = *Ws[l];
+    TORCH_CHECK(W.dim() == 2 && W.size(1) == width[l] && W.size(0) >= 1, b.name, ": W", l + 1,
+                " must be [n", l + 1, ", ", width[l], "]");
+    check_dense_on_device(W, b, "W", torch::kFloat32, W.numel());
+    width[l + 1] = W.size(0);
+    TORCH_CHECK(bs[l]->dim() == 1, b.name, ": b", l + 1, " must be 1-D");
+    check_dense_on_device(*bs[l], b, "b", torch::kFloat32, width[l + 1]);
+  }
+  const int ks = mlp_ks((int)d);
+  TORCH_CHECK(width[1] <= 64 * ks && width[2] <= 32 * ks && width[3] <= 32 * ks, b.name,
+              ": layer widths ", width[1], ", ", width[2], ", ", width[3], " beyond ", 64 * ks, ", ",
+              32 * ks, ", ", 32 * ks, " for ", d, " columns");
+  TORCH_CHECK(shift.device() == b.device && scale.device() == b.device, b.name,
+              ": shift and scale must be on the columns' device");
+  auto device = b.device;
+  const int64_t n = b.maxn;
+  const int n1 = (int)width[1], n2 = (int)width[2], n3 = (int)width[3];
+  std::vector<torch::Tensor> res;
+  if (outs) {
+    check_count(outs->size(), (size_t)n3, b.name, "outs");
+    for (auto &t : *outs) {
+      check_dense_on_device(t, b, "outs", torch::kFloat32, n);
+      TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, b.name,
+                  ": outs must start at a 16-byte aligned address");
+    }
+    res = *outs;
+  } else {
+    for (int c = 0; c < n3; ++c) res.push_back(torch::empty({n}, on(device, torch::kFloat32)));
+  }
+  if (n == 0) return res;
+  auto shift_d = shift.to(torch::kFloat32).contiguous();
+  auto scale_d = scale.to(torch::kFloat32).contiguous();
+  auto img = torch::empty({mlp_image_shorts((int)d, n1, n2, n3)}, on(device, torch::kInt16));
+  auto dptr = upload(b.ptrs, device);
+  std::vector<int64_t> optrs;
+  for (auto &t : res) optrs.push_back((int64_t)t.data_ptr());
+  auto dout = upload(optrs, device);
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_MLP_BLOCKS")) blocks = atoi(e);
+  check_hip(anovos_mlp_weight_image(W1.data_ptr<float>(), b1.data_ptr<float>(),
+                                    W2.data_ptr<float>(), b2.data_ptr<float>(),
+                                    W3.data_ptr<float>(), b3.data_ptr<float>(), (int)d, n1, n2, n3,
+                                    (uint16_t *)img.data_ptr<int16_t>(), current_stream()),
+            "anovos_mlp_weight_image");
+  check_hip(anovos_mlp_encode(ptr_table<const void>(dptr), n, (int)d, shift_d.data_ptr<float>(),
+                              scale_d.data_ptr<float>(),
+                              (const uint16_t *)img.data_ptr<int16_t>(), n1, n2, n3, blocks,
+                              ptr_table<float>(dout), current_stream()),
+            "anovos_mlp_encode");
+  return res;
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1670,6 +1739,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cols"), py::arg("rows"), py::arg("center"), py::arg("donors"), py::arg("target"),
         py::arg("k"), py::arg("candidates") = false);
   m.attr("KNN_CAND") = KNN_CAND;
+  m.def("mlp_encode_bf16x2", &mlp_encode_bf16x2,
+        "three-layer ReLU MLP of standardized columns as n3 separate f32 columns, fused "
+        "split-bf16 MFMA (K30)",
+        py::arg("cols"), py::arg("shift"), py::arg("scale"), py::arg("W1"), py::arg("b1"),
+        py::arg("W2"), py::arg("b2"), py::arg("W3"), py::arg("b3"), py::arg("outs") = py::none());
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

@@ -3,7 +3,7 @@
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
 // grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip,
-// project_columns.hip, split_gram.hip):
+// project_columns.hip, split_gram.hip, knn_impute.hip, mlp_encode.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -124,6 +124,36 @@ __host__ __device__ constexpr int knn_tiles(int s) {
 // uint16 entries of one donor tile of the image: 5 planes x KS k-steps x 64
 // lanes x 8 columns
 __host__ __device__ constexpr int knn_tile_shorts(int m) { return 5 * (knn_mpad(m) / 32) * 512; }
+// K30: fused three-layer MLP encode (mlp_encode.hip). d <= MLP_MAX_COLS
+// input columns pad to KS = mlp_ks(d) k-steps of 32; the layer widths are
+// n1 <= 64 * KS, n2 <= 32 * KS, n3 <= 32 * KS (every autoencoder shape of
+// d <= 160 columns: n1 = 2 d, n3 <= n2 <= d). n1 and n2 pad to 32 - two
+// 16-component tiles make one k-step of the next layer - n3 to 16. The
+// weight image is a sequence of ring stages of mlp_stage_shorts(d) uint16,
+// one per tile of layers 1 and 3 and mlp_l2_stages() per tile of layer 2
+// (whose k-steps number up to 2 * KS: a stage holds KS of them), followed
+// by the biases as f32, 16 per tile.
+constexpr int MLP_MAX_COLS = 160;
+constexpr int MLP_SLAB_ROWS = ROWQUAD_SLAB_ROWS;
+__host__ __device__ constexpr int mlp_ks(int d) { return (d + 31) / 32; }
+__host__ __device__ constexpr int mlp_tiles12(int width) { return 2 * ((width + 31) / 32); }
+__host__ __device__ constexpr int mlp_tiles3(int n3) { return (n3 + 15) / 16; }
+__host__ __device__ constexpr int mlp_l2_stages(int d, int n1) {
+  return (n1 + 31) / 32 > mlp_ks(d) ? 2 : 1;
+}
+__host__ __device__ constexpr int mlp_stages(int d, int n1, int n2, int n3) {
+  return mlp_tiles12(n1) + mlp_tiles12(n2) * mlp_l2_stages(d, n1) + mlp_tiles3(n3);
+}
+// two planes x KS k-steps x 64 lanes x 8 inputs
+__host__ __device__ constexpr int mlp_stage_shorts(int d) { return 2 * mlp_ks(d) * 512; }
+__host__ __device__ constexpr int64_t mlp_image_shorts(int d, int n1, int n2, int n3) {
+  return (int64_t)mlp_stages(d, n1, n2, n3) * mlp_stage_shorts(d) +
+         2 * 16 * (mlp_tiles12(n1) + mlp_tiles12(n2) + mlp_tiles3(n3));
+}
+__host__ __device__ constexpr bool mlp_widths_ok(int d, int n1, int n2, int n3) {
+  return d >= 1 && d <= MLP_MAX_COLS && n1 >= 1 && n1 <= 64 * mlp_ks(d) && n2 >= 1 &&
+         n2 <= 32 * mlp_ks(d) && n3 >= 1 && n3 <= 32 * mlp_ks(d);
+}
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
 // one wave iteration of a 4-wide loop; one more group holds the <= 3 rows
@@ -309,4 +339,16 @@ int anovos_knn_impute(const void *const *cols, int64_t n, int m, const int64_t *
                       const float *mean_hi, const float *mean_lo, const float *donors, int s,
                       int target, int k, const uint16_t *img, int blocks, float *est, int *idx,
                       float *d2, int *cand_idx, float *cand_d2, hipStream_t stream);
+// mlp_encode.hip: W1 [n1, d], W2 [n2, n1], W3 [n3, n2] f32 row-major, b1 / b2
+// / b3 their biases; widths within mlp_widths_ok. The image kernel fills img
+// (mlp_image_shorts uint16, 16-byte aligned) once per call; the encode
+// kernel writes y = W3 relu(W2 relu(W1 z + b1) + b2) + b3 of every row into
+// the columns outs[c] (n3 device pointers, each n floats, 16-byte aligned).
+// n >= 1. blocks <= 0: one wave of resident blocks.
+int anovos_mlp_weight_image(const float *W1, const float *b1, const float *W2, const float *b2,
+                            const float *W3, const float *b3, int d, int n1, int n2, int n3,
+                            uint16_t *img, hipStream_t stream);
+int anovos_mlp_encode(const void *const *cols, int64_t n, int d, const float *shift,
+                      const float *scale, const uint16_t *img, int n1, int n2, int n3, int blocks,
+                      float *const *outs, hipStream_t stream);
 }
