@@ -28,6 +28,7 @@ import torch
 
 from anovos_amd.core import dist
 from anovos_amd.core.frame import AnovosFrame, Column
+from anovos_amd.ops import chain as chain_ops
 from anovos_amd.ops import knn as knn_ops
 from anovos_amd.ops import stats as stats_ops
 from anovos_amd.shared.utils import attributeType_segregation, normalize_columns
@@ -80,10 +81,15 @@ def imputation_sklearn(
 ):
     """KNN / IterativeImputer(regression) — reference transformers.py:1677-2020.
 
-    apply_precision (KNN only; ignored for regression): "fp64" applies the
-    model with fp64 torch GEMMs; "bf16x2" with the K29 kernel (ops/knn.py) on
-    the HIP backend, where a model within its limits (128 columns, 8
-    neighbours, 65 536 donors) needs no [rows, donors] matrix."""
+    apply_precision: "fp64" applies the model with fp64 torch ops. "bf16x2"
+    applies it on the HIP backend with a kernel that reads the frame once:
+    KNN with K29 (ops/knn.py), where a model within its limits (128 columns,
+    8 neighbours, 65 536 donors) needs no [rows, donors] matrix; regression
+    with K31 (ops/chain.py), which replays the fitted chain of linear
+    predicts per row and writes only the null entries - for a model of 2 to
+    160 columns, at most 32 rounds, linear estimators and one visiting order
+    (sklearn's default), otherwise the fp64 path runs. KNN refuses any other
+    value; regression ignores it and runs the fp64 path."""
     from sklearn.experimental import enable_iterative_imputer  # noqa: F401
     from sklearn.impute import IterativeImputer, KNNImputer
 
@@ -128,6 +134,21 @@ def imputation_sklearn(
     # only ROWS THAT HAVE a missing value go through the solver.
     dev = idf.device
     filled = {}  # column -> (rows, values) of its null entries
+    chain = None
+    if method_type == "regression" and apply_precision == "bf16x2" and chain_ops.kernel_serves(idf, cols):
+        chain = chain_ops.chain_model(model, len(cols))
+    if chain is not None:
+        # K31 writes the null entries of the output columns in place: no
+        # stacked copy of the rows that have a null, no pass per step
+        clones = {c: idf.col(c).data.clone() for c in cols}
+        chain_ops.chain_impute(idf, cols, chain, clones)
+        odf = idf
+        for c in cols:
+            name = c if output_mode == "replace" else c + "_imputed"
+            odf = odf.with_column(name, Column(name, idf.col(c).dtype, clones[c]))
+        if print_impact:
+            print(odf.columns)
+        return odf
     if method_type == "KNN" and apply_precision == "bf16x2":
         filled = knn_ops.knn_impute(idf, cols, model._fit_X, int(model.n_neighbors))
     else:

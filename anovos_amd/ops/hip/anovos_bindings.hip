@@ -1,7 +1,7 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
 // pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip,
-// knn_impute.hip, mlp_encode.hip).
+// knn_impute.hip, mlp_encode.hip, chain_impute.hip).
 // Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
 // from the caller's current torch HIP stream so kernels compose with the
 // engine's side-stream overlap
@@ -1062,6 +1062,78 @@ std::vector<torch::Tensor> mlp_encode_bf16x2(
   return res;
 }
 
+// K31: regression imputation apply (chain_impute.hip). cols are the m f32
+// columns (NaN = null); `center` [m] is taken as fp64 and split into two
+// floats on the host; `order` int32 [m_s] names the target column of every
+// step of a round; C f32 [R, m_s, m], beta f32 [R, m_s], lo / hi f32 [m]
+// (clip bounds of the centred values, +-inf allowed) are dense on the
+// columns' device. `outs` has one entry per column, None or a dense f32
+// tensor of the column's length: for every null x_j[i] of a column j that is
+// in `order` and has outs[j], outs[j][i] = z_j + (float)center_j. Nothing
+// else is written.
+void chain_impute_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor center,
+                         torch::Tensor order, torch::Tensor C, torch::Tensor beta,
+                         torch::Tensor lo, torch::Tensor hi,
+                         std::vector<std::optional<torch::Tensor>> outs) {
+  ColumnBatch b = gather_columns(cols, "chain_impute_bf16x2", F32, /*equal_len=*/true);
+  const int64_t m = b.ncols();
+  TORCH_CHECK(m >= 2 && m <= CHAIN_MAX_COLS, b.name, ": ", m, " columns, expected 2 .. ",
+              CHAIN_MAX_COLS, " (CHAIN_MAX_COLS)");
+  TORCH_CHECK(C.dim() == 3 && C.size(2) == m, b.name, ": C must be [R, m_s, ", m, "]");
+  const int64_t R = C.size(0), m_s = C.size(1);
+  TORCH_CHECK(R >= 1 && R <= CHAIN_MAX_ROUNDS, b.name, ": ", R, " rounds, expected 1 .. ",
+              CHAIN_MAX_ROUNDS, " (CHAIN_MAX_ROUNDS)");
+  TORCH_CHECK(m_s >= 1 && m_s <= m, b.name, ": ", m_s, " steps per round, expected 1 .. ", m);
+  check_dense_on_device(C, b, "C", torch::kFloat32, R * m_s * m);
+  check_count((size_t)beta.numel(), (size_t)(R * m_s), b.name, "beta");
+  check_dense_on_device(beta, b, "beta", torch::kFloat32, R * m_s);
+  check_count((size_t)lo.numel(), (size_t)m, b.name, "lo");
+  check_dense_on_device(lo, b, "lo", torch::kFloat32, m);
+  check_count((size_t)hi.numel(), (size_t)m, b.name, "hi");
+  check_dense_on_device(hi, b, "hi", torch::kFloat32, m);
+  check_count((size_t)order.numel(), (size_t)m_s, b.name, "order");
+  TORCH_CHECK(order.scalar_type() == torch::kInt32 && order.is_contiguous(), b.name,
+              ": order must be a contiguous int32 tensor");
+  auto order_h = order.cpu();
+  std::vector<int> ord(order_h.data_ptr<int32_t>(), order_h.data_ptr<int32_t>() + m_s);
+  std::vector<char> seen((size_t)m, 0);
+  for (int j : ord) {
+    TORCH_CHECK(j >= 0 && j < m, b.name, ": order entry ", j, " outside the ", m, " columns");
+    TORCH_CHECK(!seen[j], b.name, ": order names column ", j, " twice");
+    seen[j] = 1;
+  }
+  auto ctr = host_f64(center, (size_t)m, b.name, "center");
+  check_count(outs.size(), (size_t)m, b.name, "outs");
+  const int64_t n = b.maxn;
+  std::vector<int64_t> optrs;
+  for (auto &t : outs) {
+    if (t) check_dense_on_device(*t, b, "outs", torch::kFloat32, n);
+    optrs.push_back(t ? (int64_t)t->data_ptr() : 0);
+  }
+  if (n == 0) return;
+  auto device = b.device;
+  std::vector<float> mh((size_t)m), ml((size_t)m);
+  for (int64_t j = 0; j < m; ++j) {
+    mh[j] = (float)ctr[j];
+    ml[j] = (float)(ctr[j] - (double)mh[j]);
+  }
+  auto mh_d = upload(mh, device), ml_d = upload(ml, device), ord_d = upload(ord, device);
+  auto dptr = upload(b.ptrs, device), dout = upload(optrs, device);
+  auto img = torch::empty({chain_image_shorts((int)m, (int)m_s, (int)R)}, on(device, torch::kInt16));
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_CHAIN_BLOCKS")) blocks = atoi(e);
+  check_hip(anovos_chain_image(C.data_ptr<float>(), beta.data_ptr<float>(), (int)m, (int)m_s,
+                               (int)R, (uint16_t *)img.data_ptr<int16_t>(), current_stream()),
+            "anovos_chain_image");
+  check_hip(anovos_chain_impute(ptr_table<const void>(dptr), n, (int)m, (int)m_s, (int)R,
+                                mh_d.data_ptr<float>(), ml_d.data_ptr<float>(),
+                                ord_d.data_ptr<int32_t>(), C.data_ptr<float>(),
+                                (const uint16_t *)img.data_ptr<int16_t>(), lo.data_ptr<float>(),
+                                hi.data_ptr<float>(), blocks, ptr_table<float>(dout),
+                                current_stream()),
+            "anovos_chain_impute");
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1744,6 +1816,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "split-bf16 MFMA (K30)",
         py::arg("cols"), py::arg("shift"), py::arg("scale"), py::arg("W1"), py::arg("b1"),
         py::arg("W2"), py::arg("b2"), py::arg("W3"), py::arg("b3"), py::arg("outs") = py::none());
+  m.def("chain_impute_bf16x2", &chain_impute_bf16x2,
+        "regression imputation apply: the fitted chain of linear predicts replayed per row into "
+        "the null entries of caller-owned columns, split-bf16 MFMA observed part (K31)",
+        py::arg("cols"), py::arg("center"), py::arg("order"), py::arg("C"), py::arg("beta"),
+        py::arg("lo"), py::arg("hi"), py::arg("outs"));
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

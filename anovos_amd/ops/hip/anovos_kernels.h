@@ -3,7 +3,8 @@
 // Included by the bindings (anovos_bindings.hip) and by every file that
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
 // grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip,
-// project_columns.hip, split_gram.hip, knn_impute.hip, mlp_encode.hip):
+// project_columns.hip, split_gram.hip, knn_impute.hip, mlp_encode.hip,
+// chain_impute.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -153,6 +154,24 @@ __host__ __device__ constexpr int64_t mlp_image_shorts(int d, int n1, int n2, in
 __host__ __device__ constexpr bool mlp_widths_ok(int d, int n1, int n2, int n3) {
   return d >= 1 && d <= MLP_MAX_COLS && n1 >= 1 && n1 <= 64 * mlp_ks(d) && n2 >= 1 &&
          n2 <= 32 * mlp_ks(d) && n3 >= 1 && n3 <= 32 * mlp_ks(d);
+}
+// K31: regression (IterativeImputer) apply as a row-local chain
+// (chain_impute.hip). m columns pad to KS = chain_ks(m) k-steps of 32, the
+// m_s steps of a round to chain_tiles(m_s) tiles of 16. The coefficient
+// image is one stage of chain_stage_shorts(m) uint16 per (round, step tile),
+// followed by the intercepts as f32, 16 per stage.
+constexpr int CHAIN_MAX_COLS = 160;
+constexpr int CHAIN_MAX_ROUNDS = 32;
+constexpr int CHAIN_SLAB_ROWS = ROWQUAD_SLAB_ROWS;
+__host__ __device__ constexpr int chain_ks(int m) { return (m + 31) / 32; }
+__host__ __device__ constexpr int chain_tiles(int m_s) { return (m_s + 15) / 16; }
+// two planes x KS k-steps x 64 lanes x 8 columns
+__host__ __device__ constexpr int chain_stage_shorts(int m) { return 2 * chain_ks(m) * 512; }
+__host__ __device__ constexpr int64_t chain_image_shorts(int m, int m_s, int R) {
+  return (int64_t)R * chain_tiles(m_s) * (chain_stage_shorts(m) + 2 * 16);
+}
+__host__ __device__ constexpr bool chain_shape_ok(int m, int m_s, int R) {
+  return m >= 2 && m <= CHAIN_MAX_COLS && m_s >= 1 && m_s <= m && R >= 1 && R <= CHAIN_MAX_ROUNDS;
 }
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
@@ -351,4 +370,20 @@ int anovos_mlp_weight_image(const float *W1, const float *b1, const float *W2, c
 int anovos_mlp_encode(const void *const *cols, int64_t n, int d, const float *shift,
                       const float *scale, const uint16_t *img, int n1, int n2, int n3, int blocks,
                       float *const *outs, hipStream_t stream);
+// chain_impute.hip: C is f32 [R, m_s, m] row-major (zero outside a step's
+// neighbours and at its own target), beta f32 [R, m_s], order int32 [m_s]
+// with distinct entries in [0, m), mean_hi + mean_lo the fp64 centre split
+// into two floats, lo / hi f32 [m] clip bounds of the centred values (may be
+// -inf / +inf); shapes within chain_shape_ok. The image kernel fills img
+// (chain_image_shorts uint16, 16-byte aligned) once per call; the apply
+// kernel writes z_j + mean_hi[j] to outs[j][i] for every null x_j[i] of a
+// column j that is in order and has outs[j] != null (m device pointers, each
+// n floats), and nothing else. n >= 1. blocks <= 0: one wave of resident
+// blocks.
+int anovos_chain_image(const float *C, const float *beta, int m, int m_s, int R, uint16_t *img,
+                       hipStream_t stream);
+int anovos_chain_impute(const void *const *cols, int64_t n, int m, int m_s, int R,
+                        const float *mean_hi, const float *mean_lo, const int *order,
+                        const float *C, const uint16_t *img, const float *lo, const float *hi,
+                        int blocks, float *const *outs, hipStream_t stream);
 }
