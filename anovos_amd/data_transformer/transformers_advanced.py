@@ -28,6 +28,7 @@ import torch
 
 from anovos_amd.core import dist
 from anovos_amd.core.frame import AnovosFrame, Column
+from anovos_amd.ops import als as als_ops
 from anovos_amd.ops import chain as chain_ops
 from anovos_amd.ops import knn as knn_ops
 from anovos_amd.ops import stats as stats_ops
@@ -233,15 +234,35 @@ def imputation_matrixFactorization(
     rank: int = 10,
     max_iter: int = 20,
     reg: float = 0.01,
+    precision: str = "fp32",
 ):
     """ALS matrix factorization over the (row, attribute) value matrix —
     reference transformers.py:2022-2257 (MLlib ALS maxIter=20, reg=0.01).
-    Torch-native alternating ridge solves on the standardized matrix."""
+    Torch-native alternating ridge solves on the standardized matrix.
+
+    precision: "fp32" runs those torch solves on stacked copies of the frame,
+    every rank fitting its own V. "bf16x2" runs ops/als.py instead: on the HIP
+    backend both halves of a sweep on K32 (up to 160 columns, rank up to 16),
+    which read the frame in place and write only the null entries; one V for
+    all ranks (one all-reduce per sweep); the fp64 definition in row slabs on
+    the CPU backend or beyond the kernel's limits."""
+    if precision not in ("fp32", "bf16x2"):
+        raise TypeError("Invalid input for precision")
     cols = _resolve_missing_cols(ctx, idf, list_of_cols, drop_cols, stats_missing)
     cols = [c for c in cols if c != id_col]
     if not cols:
         warnings.warn("No Imputation performed - No numerical column(s) with missing values")
         return idf
+    if precision == "bf16x2":
+        clones = {c: idf.col(c).data.clone() for c in cols}
+        als_ops.als_impute(idf, cols, rank, max_iter, reg, clones)
+        odf = idf
+        for c in cols:
+            name = c if output_mode == "replace" else c + "_imputed"
+            odf = odf.with_column(name, Column(name, idf.col(c).dtype, clones[c]))
+        if print_impact:
+            print(odf.columns)
+        return odf
     dev = idf.device
     X = torch.stack([idf.col(c).data.to(torch.float32) for c in cols], dim=1).to(dev)
     mask = ~torch.isnan(X)

@@ -1,7 +1,7 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
 // pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip,
-// knn_impute.hip, mlp_encode.hip, chain_impute.hip).
+// knn_impute.hip, mlp_encode.hip, chain_impute.hip, als_sweep.hip).
 // Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
 // from the caller's current torch HIP stream so kernels compose with the
 // engine's side-stream overlap
@@ -1134,6 +1134,135 @@ void chain_impute_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor center,
             "anovos_chain_impute");
 }
 
+// K32 (als_sweep.hip): what both halves of an ALS sweep take besides the
+// columns - the fp64 centre split into two floats, scale = 1 / sd as f32.
+struct AlsFrame {
+  torch::Tensor dptr, mean_hi, mean_lo, scale;
+};
+
+AlsFrame als_frame(const ColumnBatch &b, const torch::Tensor &center, const torch::Tensor &scale) {
+  const size_t m = (size_t)b.ncols();
+  TORCH_CHECK(m <= (size_t)ALS_MAX_COLS, b.name, ": ", m, " columns, expected 1 .. ", ALS_MAX_COLS,
+              " (ALS_MAX_COLS)");
+  for (int64_t p : b.ptrs)
+    TORCH_CHECK(p % 16 == 0, b.name, ": columns must be 16-byte aligned");
+  auto ctr = host_f64(center, m, b.name, "center");
+  auto sc = host_f64(scale, m, b.name, "scale");
+  std::vector<float> mh(m), ml(m), s(m);
+  for (size_t j = 0; j < m; ++j) {
+    mh[j] = (float)ctr[j];
+    ml[j] = (float)(ctr[j] - (double)mh[j]);
+    s[j] = (float)sc[j];
+  }
+  return {upload(b.ptrs, b.device), upload(mh, b.device), upload(ml, b.device),
+          upload(s, b.device)};
+}
+
+// K32, row half: u_r = (sum_j m_rj v_j v_j^T + reg max(n_r, 1) I)^-1 sum_j z_rj v_j
+// per row, z = isnan(x) ? 0 : (x - center) * scale. V is f32 [m, k], 1 <= k
+// <= ALS_MAX_RANK, padded here to KR = als_kr(k) components. Returns (U, N):
+// U (with want_u) an f32 [KR, n] view whose rows are contiguous component
+// columns; N (with normal) f32 [n, T + KR], the packed lower triangle of A
+// and b before the regulariser. `outs`, if given, has one entry per column,
+// None or a dense f32 tensor of the column's length: for every null x_j[i]
+// with outs[j], outs[j][i] = fmaf(u_i . v_j, sd_j, (float)center_j). Nothing
+// else is written.
+py::tuple als_row_solve_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor center,
+                               torch::Tensor scale, torch::Tensor sd, torch::Tensor V, double reg,
+                               std::optional<std::vector<std::optional<torch::Tensor>>> outs,
+                               bool want_u, bool normal) {
+  ColumnBatch b = gather_columns(cols, "als_row_solve_bf16x2", F32, /*equal_len=*/true);
+  const int64_t m = b.ncols();
+  AlsFrame f = als_frame(b, center, scale);
+  TORCH_CHECK(V.dim() == 2 && V.size(0) == m, b.name, ": V must be [", m, ", rank]");
+  const int64_t k = V.size(1);
+  TORCH_CHECK(k >= 1 && k <= ALS_MAX_RANK, b.name, ": rank ", k, ", expected 1 .. ", ALS_MAX_RANK,
+              " (ALS_MAX_RANK)");
+  check_dense_on_device(V, b, "V", torch::kFloat32, m * k);
+  TORCH_CHECK(reg > 0.0, b.name, ": reg must be positive");
+  auto sd_h = host_f64(sd, (size_t)m, b.name, "sd");
+  const int64_t n = b.maxn;
+  std::vector<int64_t> optrs;
+  if (outs) {
+    check_count(outs->size(), (size_t)m, b.name, "outs");
+    for (auto &t : *outs) {
+      if (t) check_dense_on_device(*t, b, "outs", torch::kFloat32, n);
+      optrs.push_back(t ? (int64_t)t->data_ptr() : 0);
+    }
+  }
+  auto device = b.device;
+  const int kr = als_kr((int)k), NT = als_tri(kr) + kr;
+  const int64_t ldu = (n + ALS_SLAB_ROWS - 1) / ALS_SLAB_ROWS * ALS_SLAB_ROWS;
+  torch::Tensor U, N;
+  if (want_u) U = torch::empty({kr, ldu}, on(device, torch::kFloat32));
+  if (normal) N = torch::empty({n, NT}, on(device, torch::kFloat32));
+  py::object u_out = want_u ? py::cast(U.narrow(1, 0, n)) : py::none();
+  py::object n_out = normal ? py::cast(N) : py::none();
+  if (n == 0) return py::make_tuple(u_out, n_out);
+  auto Vp = torch::zeros({m, kr}, on(device, torch::kFloat32));
+  Vp.narrow(1, 0, k).copy_(V);
+  std::vector<float> sdf(sd_h.begin(), sd_h.end());
+  auto sd_d = upload(sdf, device);
+  torch::Tensor dout;
+  if (outs) dout = upload(optrs, device);
+  auto img = torch::empty({als_row_image_shorts((int)m, kr)}, on(device, torch::kInt16));
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_ALS_BLOCKS")) blocks = atoi(e);
+  check_hip(anovos_als_row_image(Vp.data_ptr<float>(), (int)m, kr,
+                                 (uint16_t *)img.data_ptr<int16_t>(), current_stream()),
+            "anovos_als_row_image");
+  check_hip(anovos_als_row_solve(ptr_table<const void>(f.dptr), n, (int)m, kr,
+                                 f.mean_hi.data_ptr<float>(), f.mean_lo.data_ptr<float>(),
+                                 f.scale.data_ptr<float>(), sd_d.data_ptr<float>(),
+                                 Vp.data_ptr<float>(), (const uint16_t *)img.data_ptr<int16_t>(),
+                                 (float)reg, blocks, outs ? ptr_table<float>(dout) : nullptr,
+                                 want_u ? U.data_ptr<float>() : nullptr, ldu,
+                                 normal ? N.data_ptr<float>() : nullptr, current_stream()),
+            "anovos_als_row_solve");
+  return py::make_tuple(u_out, n_out);
+}
+
+// K32, column half: per column j the packed lower triangle of H_j = sum_r
+// m_rj u_r u_r^T followed by g_j = sum_r z_rj u_r, fp64 [m, T + KR]. U is f32
+// [KR, n], KR in {4, 8, 12, 16}, its rows contiguous and 16-byte aligned (a
+// view of a wider buffer will do: what als_row_solve_bf16x2 returns).
+torch::Tensor als_col_normal_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor center,
+                                    torch::Tensor scale, torch::Tensor U) {
+  ColumnBatch b = gather_columns(cols, "als_col_normal_bf16x2", F32, /*equal_len=*/true);
+  const int64_t m = b.ncols(), n = b.maxn;
+  AlsFrame f = als_frame(b, center, scale);
+  TORCH_CHECK(U.dim() == 2 && U.size(1) == n && U.device() == b.device &&
+                  U.scalar_type() == torch::kFloat32,
+              b.name, ": U must be a float32 [KR, ", n, "] tensor on the columns' device");
+  const int64_t kr = U.size(0);
+  TORCH_CHECK(kr >= 4 && kr <= ALS_MAX_RANK && kr % 4 == 0, b.name, ": U has ", kr,
+              " components, expected 4, 8, 12 or 16");
+  const int64_t ldu = U.stride(0);
+  TORCH_CHECK((n <= 1 || U.stride(1) == 1) && ldu % 4 == 0 && ldu >= n &&
+                  (int64_t)U.data_ptr() % 16 == 0,
+              b.name, ": the rows of U must be contiguous and 16-byte aligned");
+  const int NT = als_tri((int)kr) + (int)kr;
+  auto out = torch::zeros({m, NT}, on(b.device, torch::kFloat64));
+  if (n == 0) return out;
+  // Row split: one wave of resident blocks over the groups, each block a
+  // contiguous range of macro-slabs; fewer chunks where the fp64 partials
+  // would pass 16 MiB, never more than there are macro-slabs.
+  const int64_t macro_total = (n + ALS_SLAB_ROWS - 1) / ALS_SLAB_ROWS;
+  const int64_t per_chunk = als_col_chunk_doubles((int)m, (int)kr);
+  int64_t chunks = std::max<int64_t>(1, anovos_als_col_grid((int)kr) / als_groups((int)m));
+  chunks = std::min<int64_t>(chunks, ((int64_t)16 << 20) / (per_chunk * 8));
+  if (const char *e = getenv("ANOVOS_ALS_CHUNKS")) chunks = atoll(e);
+  const int row_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(chunks, macro_total), 4096));
+  auto partials = torch::empty({row_chunks * per_chunk}, on(b.device, torch::kFloat64));
+  check_hip(anovos_als_col_normal(ptr_table<const void>(f.dptr), n, (int)m, (int)kr,
+                                  f.mean_hi.data_ptr<float>(), f.mean_lo.data_ptr<float>(),
+                                  f.scale.data_ptr<float>(), U.data_ptr<float>(), ldu, row_chunks,
+                                  partials.data_ptr<double>(), out.data_ptr<double>(),
+                                  current_stream()),
+            "anovos_als_col_normal");
+  return out;
+}
+
 // K5 fused: multi-column code counts (+ null slot per column).
 // Returns flat int64 tensor of length sum(sizes_i + 1); with null_masks
 // (flat, masks, partitions), where the columns that count in LDS get their
@@ -1821,6 +1950,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "the null entries of caller-owned columns, split-bf16 MFMA observed part (K31)",
         py::arg("cols"), py::arg("center"), py::arg("order"), py::arg("C"), py::arg("beta"),
         py::arg("lo"), py::arg("hi"), py::arg("outs"));
+  m.def("als_row_solve_bf16x2", &als_row_solve_bf16x2,
+        "ALS row half: masked normal equations on split-bf16 MFMA and a register Cholesky per "
+        "row; U, predictions at the null entries, or the normal equations (K32)",
+        py::arg("cols"), py::arg("center"), py::arg("scale"), py::arg("sd"), py::arg("V"),
+        py::arg("reg"), py::arg("outs") = py::none(), py::arg("want_u") = true,
+        py::arg("normal") = false);
+  m.def("als_col_normal_bf16x2", &als_col_normal_bf16x2,
+        "ALS column half: per-column masked normal equations, split-bf16 MFMA with fp64 flushes (K32)",
+        py::arg("cols"), py::arg("center"), py::arg("scale"), py::arg("U"));
+  m.attr("ALS_MAX_RANK") = ALS_MAX_RANK;
+  m.attr("ALS_MAX_COLS") = ALS_MAX_COLS;
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");
   m.def("bucketize_columns_float", &bucketize_columns_float, "bucketize to float bin labels (K6)");
   m.def("bucketize_columns_float_counts", &bucketize_columns_float_counts,

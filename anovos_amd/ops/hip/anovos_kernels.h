@@ -4,7 +4,7 @@
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
 // grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip,
 // project_columns.hip, split_gram.hip, knn_impute.hip, mlp_encode.hip,
-// chain_impute.hip):
+// chain_impute.hip, als_sweep.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -172,6 +172,35 @@ __host__ __device__ constexpr int64_t chain_image_shorts(int m, int m_s, int R) 
 }
 __host__ __device__ constexpr bool chain_shape_ok(int m, int m_s, int R) {
   return m >= 2 && m <= CHAIN_MAX_COLS && m_s >= 1 && m_s <= m && R >= 1 && R <= CHAIN_MAX_ROUNDS;
+}
+// K32: the two halves of an ALS sweep (als_sweep.hip). The rank pads to
+// KR = als_kr(rank) in {4, 8, 12, 16}; a symmetric KR x KR matrix travels as
+// its als_tri(KR) lower entries, (a, b) with a >= b at a (a + 1) / 2 + b,
+// followed by the KR entries of the right-hand side. Entries go to the MFMA
+// in tiles of 16: the products (and one slot of ones, which counts the
+// observed entries), then one tile for the right-hand side. The m columns
+// pad to als_ks(m) k-steps of 32 (row half) and go in als_groups(m) groups
+// of 64 (column half).
+constexpr int ALS_MAX_RANK = 16;
+constexpr int ALS_MAX_COLS = 160;
+constexpr int ALS_SLAB_ROWS = ROWQUAD_SLAB_ROWS;
+__host__ __device__ constexpr int als_kr(int rank) { return (rank + 3) / 4 * 4; }
+__host__ __device__ constexpr int als_tri(int kr) { return kr * (kr + 1) / 2; }
+__host__ __device__ constexpr int als_tiles(int kr) { return (als_tri(kr) + 1 + 15) / 16 + 1; }
+__host__ __device__ constexpr int als_ks(int m) { return (m + 31) / 32; }
+__host__ __device__ constexpr int als_groups(int m) { return (m + 63) / 64; }
+// uint16 entries of the row half's image: tiles x two planes x KS k-steps x
+// 64 lanes x 8 columns
+__host__ __device__ constexpr int64_t als_row_image_shorts(int m, int kr) {
+  return (int64_t)als_tiles(kr) * 2 * als_ks(m) * 512;
+}
+// doubles of the column half's partials per row chunk: groups x 4 waves x
+// tiles x 256
+__host__ __device__ constexpr int64_t als_col_chunk_doubles(int m, int kr) {
+  return (int64_t)als_groups(m) * 4 * als_tiles(kr) * 256;
+}
+__host__ __device__ constexpr bool als_shape_ok(int m, int kr) {
+  return m >= 1 && m <= ALS_MAX_COLS && kr >= 4 && kr <= ALS_MAX_RANK && kr % 4 == 0;
 }
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
@@ -386,4 +415,25 @@ int anovos_chain_impute(const void *const *cols, int64_t n, int m, int m_s, int 
                         const float *mean_hi, const float *mean_lo, const int *order,
                         const float *C, const uint16_t *img, const float *lo, const float *hi,
                         int blocks, float *const *outs, hipStream_t stream);
+// als_sweep.hip: kr in {4, 8, 12, 16}, 1 <= m <= ALS_MAX_COLS; mean_hi +
+// mean_lo the fp64 centre split into two floats, scale = 1 / sd, all f32 [m].
+// Row half: V is f32 [m, kr] (padding components zero); the image kernel
+// fills img (als_row_image_shorts uint16, 16-byte aligned) once per call.
+// Any of the three outputs may be null: outs (m device pointers, null or n
+// floats each) takes fmaf(u . v_j, sd_j, mean_hi_j) at the null entries of
+// column j and nothing else; U (kr columns of ldu floats, ldu a multiple of
+// 64 and >= n, 16-byte aligned) takes the solutions, zero at the rows past
+// n; normal f32 [n, als_tri(kr) + kr] the normal equations before the
+// regulariser. n >= 1, reg > 0. blocks <= 0: one wave of resident blocks.
+// Column half: U as above with ldu a multiple of 4; out is fp64 [m,
+// als_tri(kr) + kr]; partials holds row_chunks * als_col_chunk_doubles.
+int anovos_als_row_image(const float *V, int m, int kr, uint16_t *img, hipStream_t stream);
+int anovos_als_row_solve(const void *const *cols, int64_t n, int m, int kr, const float *mean_hi,
+                         const float *mean_lo, const float *scale, const float *sd, const float *V,
+                         const uint16_t *img, float reg, int blocks, float *const *outs, float *U,
+                         int64_t ldu, float *normal, hipStream_t stream);
+int anovos_als_col_normal(const void *const *cols, int64_t n, int m, int kr, const float *mean_hi,
+                          const float *mean_lo, const float *scale, const float *U, int64_t ldu,
+                          int row_chunks, double *partials, double *out, hipStream_t stream);
+int anovos_als_col_grid(int kr);
 }

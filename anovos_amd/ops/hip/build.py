@@ -36,6 +36,7 @@ def build(verbose: bool = True) -> str:
             os.path.join(HERE, "knn_impute.hip"),
             os.path.join(HERE, "mlp_encode.hip"),
             os.path.join(HERE, "chain_impute.hip"),
+            os.path.join(HERE, "als_sweep.hip"),
         ],
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],
