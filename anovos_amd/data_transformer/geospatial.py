@@ -1,8 +1,13 @@
 """Frame-facing geospatial transformations (reference parity:
-``anovos/data_transformer/geospatial.py`` :39-1411). All math runs as
+``anovos/data_transformer/geospatial.py`` :39-1411). The math runs as
 vectorized torch ops on the GPU via geo_utils (the reference wrapped
 scalar python in per-row Spark UDFs); group aggregations (centroid, ROG)
-use scatter_reduce over id codes — no shuffles.
+use scatter_reduce over id codes — no shuffles. Polygon membership
+(``location_in_polygon``, ``location_in_country(method_type="exact")``)
+goes through ``ops.polygon.points_in_polygons``: on the GPU the banded
+ray-cast kernel K33, one call for all column pairs, which reads the two
+columns once and never forms a rows x edges matrix; on the CPU backend the
+geo_utils expression in row slabs.
 """
 
 from __future__ import annotations
@@ -16,6 +21,7 @@ import torch
 from anovos_amd.core.dtypes import NULL_CODE
 from anovos_amd.core.frame import AnovosFrame, Column
 from anovos_amd.data_transformer import geo_utils as gu
+from anovos_amd.ops.polygon import points_in_polygons
 
 EARTH_RADIUS = gu.EARTH_RADIUS
 
@@ -226,12 +232,10 @@ def location_in_polygon(idf, list_of_lat, list_of_lon, polygon, result_prefix=[]
     list_of_lat, list_of_lon = _listify(list_of_lat), _listify(list_of_lon)
     result_prefix = _listify(result_prefix) if result_prefix else []
     polys = _extract_polygons(polygon)
+    flags = points_in_polygons(idf, list(zip(list_of_lat, list_of_lon)), polys)
     odf = idf
     for k, (latc, lonc) in enumerate(zip(list_of_lat, list_of_lon)):
-        lat, lon = _num(idf, latc), _num(idf, lonc)
-        inside = gu.point_in_polygons(lat, lon, polys)
-        out = inside.to(torch.float32)
-        out = torch.where(torch.isnan(lat) | torch.isnan(lon), torch.full_like(out, float("nan")), out)
+        out = flags[k]
         pf = result_prefix[k] if result_prefix else f"{latc}_{lonc}"
         name = pf + "_in_polygon"
         odf = odf.with_column(name, Column(name, "int", out))
@@ -274,15 +278,16 @@ def location_in_country(ctx, idf, list_of_lat, list_of_lon, country, country_sha
         with open(country_shapefile_path) as f:
             gj = json.load(f)
         polys = _extract_polygons(gj)
+        flags = points_in_polygons(idf, list(zip(list_of_lat, list_of_lon)), polys)
     odf = idf
     for k, (latc, lonc) in enumerate(zip(list_of_lat, list_of_lon)):
-        lat, lon = _num(idf, latc), _num(idf, lonc)
         if method_type == "exact":
-            inside = gu.point_in_polygons(lat, lon, polys)
+            out = flags[k]
         else:
+            lat, lon = _num(idf, latc), _num(idf, lonc)
             inside = gu.point_in_country_approx(lat, lon, country)
-        out = inside.to(torch.float32)
-        out = torch.where(torch.isnan(lat) | torch.isnan(lon), torch.full_like(out, float("nan")), out)
+            out = inside.to(torch.float32)
+            out = torch.where(torch.isnan(lat) | torch.isnan(lon), torch.full_like(out, float("nan")), out)
         pf = result_prefix[k] if result_prefix else f"{latc}_{lonc}"
         name = f"{pf}_in_{str(country).lower().replace(' ', '_')}"
         odf = odf.with_column(name, Column(name, "int", out))

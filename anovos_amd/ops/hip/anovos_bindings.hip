@@ -1,7 +1,8 @@
 // Torch bindings for the anovos_amd MI355X kernels (anovos_kernels.hip,
 // corr_mfma.hip, pair_counts.hip, grouped_moments.hip, grades.hip,
 // pairwise_gram.hip, row_quadform.hip, project_columns.hip, split_gram.hip,
-// knn_impute.hip, mlp_encode.hip, chain_impute.hip, als_sweep.hip).
+// knn_impute.hip, mlp_encode.hip, chain_impute.hip, als_sweep.hip,
+// polygon_raycast.hip).
 // Compiled by torch.utils.cpp_extension with hipcc for gfx950; streams come
 // from the caller's current torch HIP stream so kernels compose with the
 // engine's side-stream overlap
@@ -1134,6 +1135,88 @@ void chain_impute_bf16x2(std::vector<torch::Tensor> cols, torch::Tensor center,
             "anovos_chain_impute");
 }
 
+// K33: point-in-polygon membership (polygon_raycast.hip). lats[p] / lons[p]
+// are the column pairs, f32 or f64, both columns of a pair alike (pairs of
+// either dtype may be mixed: one launch per dtype). The table comes from
+// ops/polygon.py edge_table as host tensors: edges fp64 [E, 5] = (px, py, qx,
+// qy, ring), band_off int32 [B + 1], band_edges int32 [L], meta fp64 [3] =
+// (ymin, ymax, scale). Everything a kernel indexes with is checked here, on
+// the host, before it is uploaded. `outs` is None or one dense f32 tensor per
+// pair; returns the outputs, 1 / 0 / NaN. bands: 0, or the B the caller
+// expects. table: "lds", "global" or "auto" (LDS when the image fits
+// PIP_LDS_BYTES).
+std::vector<torch::Tensor> points_in_polygons(std::vector<torch::Tensor> lats,
+                                              std::vector<torch::Tensor> lons, torch::Tensor edges,
+                                              torch::Tensor band_off, torch::Tensor band_edges,
+                                              torch::Tensor meta,
+                                              std::optional<std::vector<torch::Tensor>> outs,
+                                              int64_t bands, const std::string &table) {
+  const char *name = "points_in_polygons";
+  ColumnBatch all = gather_columns(lats, name, F32 | F64);
+  ColumnBatch lon_b = gather_columns(lons, name, F32 | F64);
+  check_count(lons.size(), lats.size(), name, "lons");
+  for (int p = 0; p < all.ncols(); ++p)
+    TORCH_CHECK(lon_b.dtypes[p] == all.dtypes[p] && lon_b.lens[p] == all.lens[p] &&
+                    lons[p].device() == all.device,
+                name, ": lat and lon of pair ", p, " differ in dtype, length or device");
+  TORCH_CHECK(edges.dim() == 2 && edges.size(1) == 5, name, ": edges must be [E, 5]");
+  auto edges_h = edges.to(torch::kFloat64).cpu().contiguous();
+  auto off_h = band_off.to(torch::kInt32).cpu().contiguous();
+  auto be_h = band_edges.to(torch::kInt32).cpu().contiguous();
+  auto mt = host_f64(meta, 3, name, "meta");
+  const int64_t E = edges_h.size(0), nrec = be_h.numel(), B = off_h.numel() - 1;
+  TORCH_CHECK(B >= 1 && B <= PIP_MAX_BANDS, name, ": ", B, " bands, expected 1 .. ", PIP_MAX_BANDS,
+              " (PIP_MAX_BANDS)");
+  TORCH_CHECK(bands == 0 || bands == B, name, ": band_off holds ", B, " bands, not ", bands);
+  TORCH_CHECK(nrec <= PIP_MAX_RECORDS, name, ": ", nrec, " band-edge records, at most ",
+              PIP_MAX_RECORDS, " (PIP_MAX_RECORDS)");
+  const int32_t *off = off_h.data_ptr<int32_t>(), *be = be_h.data_ptr<int32_t>();
+  TORCH_CHECK(off[0] == 0 && off[B] == nrec, name, ": band_off must run from 0 to ", nrec);
+  for (int64_t b = 0; b < B; ++b)
+    TORCH_CHECK(off[b] <= off[b + 1], name, ": band_off must ascend");
+  for (int64_t k = 0; k < nrec; ++k)
+    TORCH_CHECK(be[k] >= 0 && be[k] < E, name, ": band_edges entry ", be[k], " outside the ", E,
+                " edges");
+  TORCH_CHECK(nrec == 0 || (mt[2] > 0 && mt[2] < std::numeric_limits<double>::infinity()), name,
+              ": meta scale must be positive and finite");
+  const int64_t bytes = pip_table_bytes(nrec, (int)B);
+  TORCH_CHECK(table == "auto" || table == "lds" || table == "global", name,
+              ": table must be \"auto\", \"lds\" or \"global\"");
+  TORCH_CHECK(table != "lds" || bytes <= PIP_LDS_BYTES, name, ": a table of ", bytes,
+              " bytes does not fit the LDS budget of ", PIP_LDS_BYTES, " (PIP_LDS_BYTES)");
+  const int use_lds = table == "lds" || (table == "auto" && bytes <= PIP_LDS_BYTES);
+  auto device = all.device;
+  std::vector<torch::Tensor> res;
+  if (outs) {
+    check_count(outs->size(), lats.size(), name, "outs");
+    for (int p = 0; p < all.ncols(); ++p)
+      check_dense_on_device((*outs)[p], all, "outs", torch::kFloat32, all.lens[p]);
+    res = *outs;
+  } else {
+    for (auto &t : lats) res.push_back(torch::empty({t.numel()}, on(device, torch::kFloat32)));
+  }
+  if (all.maxn == 0) return res;
+  auto edges_d = edges_h.to(device), off_d = off_h.to(device), be_d = be_h.to(device);
+  auto image = torch::empty({bytes / 8}, on(device, torch::kFloat64));
+  check_hip(anovos_pip_table(edges_d.data_ptr<double>(), off_d.data_ptr<int32_t>(),
+                             be_d.data_ptr<int32_t>(), nrec, (int)B, image.data_ptr<double>(),
+                             current_stream()),
+            "anovos_pip_table");
+  int blocks = 0;  // one wave of resident blocks
+  if (const char *e = getenv("ANOVOS_PIP_BLOCKS")) blocks = atoi(e);
+  for (auto &b : split_by_dtype(all)) {
+    if (b.maxn == 0) continue;
+    auto dlat = upload(b.ptrs, device), dlon = upload(pick(lon_b.ptrs, b.idx), device);
+    auto dlen = upload(b.lens, device), dout = upload(out_ptrs(res, b), device);
+    check_hip(anovos_points_in_polygons(ptr_table<const void>(dlat), ptr_table<const void>(dlon),
+                                        dlen.data_ptr<int64_t>(), b.ncols(), b.maxn, b.dtype,
+                                        image.data_ptr<double>(), nrec, (int)B, mt[0], mt[1], mt[2],
+                                        use_lds, blocks, ptr_table<float>(dout), current_stream()),
+              "anovos_points_in_polygons");
+  }
+  return res;
+}
+
 // K32 (als_sweep.hip): what both halves of an ALS sweep take besides the
 // columns - the fp64 centre split into two floats, scale = 1 / sd as f32.
 struct AlsFrame {
@@ -1959,6 +2042,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("als_col_normal_bf16x2", &als_col_normal_bf16x2,
         "ALS column half: per-column masked normal equations, split-bf16 MFMA with fp64 flushes (K32)",
         py::arg("cols"), py::arg("center"), py::arg("scale"), py::arg("U"));
+  m.def("points_in_polygons", &points_in_polygons,
+        "point-in-polygon membership of (lat, lon) column pairs as f32 1 / 0 / NaN columns, banded "
+        "fp64 ray casting (K33)",
+        py::arg("lats"), py::arg("lons"), py::arg("edges"), py::arg("band_off"),
+        py::arg("band_edges"), py::arg("meta"), py::arg("outs"), py::arg("bands") = 0,
+        py::arg("table") = "auto");
+  m.attr("PIP_LDS_BYTES") = PIP_LDS_BYTES;
+  m.attr("PIP_RECORD_BYTES") = PIP_RECORD_BYTES;
   m.attr("ALS_MAX_RANK") = ALS_MAX_RANK;
   m.attr("ALS_MAX_COLS") = ALS_MAX_COLS;
   m.def("bracket_histograms_grouped", &bracket_histograms_grouped, "grouped refinement histograms (K3)");

@@ -4,7 +4,7 @@
 // defines a launcher (anovos_kernels.hip, corr_mfma.hip, pair_counts.hip,
 // grouped_moments.hip, grades.hip, pairwise_gram.hip, row_quadform.hip,
 // project_columns.hip, split_gram.hip, knn_impute.hip, mlp_encode.hip,
-// chain_impute.hip, als_sweep.hip):
+// chain_impute.hip, als_sweep.hip, polygon_raycast.hip):
 // the launchers have C linkage, so a definition whose parameter list
 // drifts from the prototype the bindings call through would link cleanly
 // and pass garbage; with the prototype in scope it fails to compile
@@ -201,6 +201,20 @@ __host__ __device__ constexpr int64_t als_col_chunk_doubles(int m, int kr) {
 }
 __host__ __device__ constexpr bool als_shape_ok(int m, int kr) {
   return m >= 1 && m <= ALS_MAX_COLS && kr >= 4 && kr <= ALS_MAX_RANK && kr % 4 == 0;
+}
+// K33: point-in-polygon membership (polygon_raycast.hip). The band-edge
+// image is nrec records of PIP_RECORD_BYTES followed by the nbands + 1 int32
+// band offsets, padded to 16 bytes. A block stages it in LDS when it fits
+// PIP_LDS_BYTES: 40 KiB leaves room for four 256-thread blocks (16 waves) on
+// a CU's 160 KiB, and the launch asks for the image's own size, so the small
+// polygons of the streaming case run eight blocks per CU. Larger images are
+// read from global memory.
+constexpr int PIP_RECORD_BYTES = 48;
+constexpr int PIP_LDS_BYTES = 40 * 1024;
+constexpr int PIP_MAX_BANDS = 65536;
+constexpr int64_t PIP_MAX_RECORDS = (int64_t)1 << 24;
+__host__ __device__ constexpr int64_t pip_table_bytes(int64_t nrec, int nbands) {
+  return nrec * PIP_RECORD_BYTES + (nbands + 1 + 3) / 4 * 16;
 }
 // Null lane masks (K1/K2+K4 and K5 emit, K10m reads): 64-bit words one
 // chunk of `per` rows owns. A group of four words covers the 256 rows of
@@ -436,4 +450,21 @@ int anovos_als_col_normal(const void *const *cols, int64_t n, int m, int kr, con
                           const float *mean_lo, const float *scale, const float *U, int64_t ldu,
                           int row_chunks, double *partials, double *out, hipStream_t stream);
 int anovos_als_col_grid(int kr);
+// polygon_raycast.hip: edges is fp64 [E, 5] = (px, py, qx, qy, ring) without
+// horizontal edges, band_off int32 [nbands + 1] ascending from 0 to nrec,
+// band_edges int32 [nrec] with entries in [0, E), every band's entries in
+// ring order. The table kernel fills image (pip_table_bytes, 16-byte
+// aligned) once per call. The membership kernel serves npairs (lat, lon)
+// column pairs of one dtype, lens[p] rows each (maxn the longest, >= 1), and
+// writes 1 / 0 / NaN to outs[p][0 .. lens[p]); band(y) is defined by ymin,
+// ymax and scale = nbands / (ymax - ymin) as the file header states. use_lds
+// needs pip_table_bytes <= PIP_LDS_BYTES. blocks <= 0: one wave of resident
+// blocks.
+int anovos_pip_table(const double *edges, const int *band_off, const int *band_edges,
+                     int64_t nrec, int nbands, void *image, hipStream_t stream);
+int anovos_points_in_polygons(const void *const *lats, const void *const *lons,
+                              const int64_t *lens, int npairs, int64_t maxn, int dtype,
+                              const void *image, int64_t nrec, int nbands, double ymin,
+                              double ymax, double scale, int use_lds, int blocks,
+                              float *const *outs, hipStream_t stream);
 }

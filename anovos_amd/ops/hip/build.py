@@ -37,6 +37,7 @@ def build(verbose: bool = True) -> str:
             os.path.join(HERE, "mlp_encode.hip"),
             os.path.join(HERE, "chain_impute.hip"),
             os.path.join(HERE, "als_sweep.hip"),
+            os.path.join(HERE, "polygon_raycast.hip"),
         ],
         extra_cflags=["-O3"],
         extra_cuda_cflags=["-O3"],
